@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the adapter-matching hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--config C2|C3|C4|C5] [--gpus N] [--steps K] [--warmup W] [--reads R]
+    python bench.py [--config C2|C3|C4|C5] [--gpus N] [--steps K] [--warmup W] [--reads R] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Default workload = BASELINE.json configs[1] ("C2"): 100 M synthetic 150 bp reads per
@@ -16,6 +16,16 @@ collective and no RCCL: the ranks only meet at the start/stop barriers and for t
 over a gloo process group on 127.0.0.1.  `python bench.py --gpus N` without a launcher starts the N ranks
 itself (one process per device) and refuses when fewer than N devices are visible.
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs and no more: it builds the workload in HBM, runs the warm-up steps, times
+the K steps, writes the outputs of the last step if --dump-outputs is given, and prints the line (metric, value, unit,
+ms_per_step, the workload's description).  Everything else is behind --full: the HIP-event times per kernel family and
+the roofline section made of them, the parity sample against the oracle, the CPU baseline, and -- for the default
+workload -- the other BASELINE configs, the p_adapter extremes and the ragged batches, each a run of its own.
+
+--dump-outputs DIR writes what the LAST timed step left in the arrays a caller of match_batch / linked_match_batch
+receives, as DIR/<name>.npy (see dump_outputs); the reads are a pure function of the arguments, so two builds of the
+library can be compared array for array.
 """
 import argparse
 import json
@@ -54,6 +64,15 @@ def parse_args(argv=None):
                          "stride, streamed end-aligned (C2, C4, C5)")
     ap.add_argument("--ragged-packed", action="store_true",
                     help="the same reads copied into a packed buffer with an offsets array: cah_match_batch_frames")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the result arrays of the last step (a fixed sample of their rows "
+                         "and whole-array sums) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-kernel HIP-event times and the "
+                         "roofline section, the parity sample against the oracle, the CPU baseline and (default workload) "
+                         "the other configs, the p_adapter extremes and the ragged batches (--no-cpu-baseline, --cpu-seconds, "
+                         "--check-reads, --no-other-configs, --other-steps and --other-cpu-seconds shape these parts and "
+                         "have no effect without --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--check-reads", type=int, default=250_000, help="reads compared with the oracle (untimed)")
@@ -298,9 +317,54 @@ def profile_fields(config, n, dom, dom_launch_ms):
     return traffic, valu, "profile taken on this build of the library (cah_build_id match)"
 
 
-def run_config(args, config, n, steps, warmup, rank, world, device, gen, check_reads, cpu_seconds, want_cpu, ragged=False):
-    """one BASELINE config: build the workload in HBM, time `steps` passes of the hot path, parity sample, roofline
-    fields, CPU baseline.  Returns the JSON-line dict (rank 0) or None (other ranks)."""
+DUMP_ROWS = 500_000        # rows of a result set that --dump-outputs writes (8 float32 values a row: 16 MB a set)
+
+
+def dump_outputs(wl, dump_dir, rank):
+    """--dump-outputs: the result arrays of the workload's last step, as float32 / float64 .npy files in dump_dir.
+
+    rows.npy                 the rows written (float64): all of them up to DUMP_ROWS, else a fixed seeded sample plus the
+                             first and the last 4096 rows (first tile, last tile, straggler flush)
+    out6.npy, status.npy     those rows of the 6-tuples and of the status array
+    best_adapter.npy         those rows of the winning adapter's index, -1 where the read has no match (the only rows
+                             where the value means something to a caller)
+    out6_column_sums.npy     the sums of the six columns over ALL rows (float64, exact), and
+    status_counts.npy        the number of rows with status 0, 1, 2 (float64): the whole array, not the sample
+    The second result set of a config (C3: the 3' stage; C5: mate 2) carries the suffix _2, the files of rank r > 0 the
+    suffix _rank<r> (their rows count from the rank's first read)."""
+    import numpy as np
+    import torch
+    os.makedirs(dump_dir, exist_ok=True)
+    n = wl.n
+    if n <= DUMP_ROWS:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        edge = 4096
+        inner = edge + np.random.default_rng(20250).choice(n - 2 * edge, DUMP_ROWS - 2 * edge, replace=False)
+        rows = np.sort(np.concatenate([np.arange(edge), inner, np.arange(n - edge, n)]).astype(np.int64))
+    idx = torch.from_numpy(rows).to(wl.outs[0].status.device)
+    tail = f"_rank{rank}" if rank else ""
+
+    def save(name, array, dtype):
+        np.save(os.path.join(dump_dir, name + tail + ".npy"), np.ascontiguousarray(array, dtype=dtype))
+
+    save("rows", rows, np.float64)
+    for k, out in enumerate(wl.outs):
+        sfx = "" if k == 0 else f"_{k + 1}"
+        status = out.status[idx]
+        save("out6" + sfx, out.out6[idx].cpu().numpy(), np.float32)
+        save("status" + sfx, status.cpu().numpy(), np.float32)
+        best = torch.where(status == 1, out.best_adapter[idx], torch.full_like(out.best_adapter[idx], -1))
+        save("best_adapter" + sfx, best.cpu().numpy(), np.float32)
+        save("out6_column_sums" + sfx, out.out6.sum(0, dtype=torch.int64).cpu().numpy(), np.float64)
+        save("status_counts" + sfx, [int((out.status == v).sum().item()) for v in (0, 1, 2)], np.float64)
+
+
+def run_config(args, config, n, steps, warmup, rank, world, device, gen, check_reads, cpu_seconds, want_cpu, ragged=False,
+               full=True, dump_dir=None):
+    """one BASELINE config: build the workload in HBM, time `steps` passes of the hot path, write the last step's outputs
+    (dump_dir) and -- full only -- parity sample, roofline fields, CPU baseline.  Returns the JSON-line dict (rank 0) or
+    None (other ranks)."""
     import torch
     import torch.distributed as dist
     from cutadapt_amd import _lib, workloads
@@ -322,7 +386,7 @@ def run_config(args, config, n, steps, warmup, rank, world, device, gen, check_r
         wl.step()
     barrier()
     L.cah_profile_reset()
-    L.cah_profile_enable(1)
+    L.cah_profile_enable(1 if full else 0)            # (HIP events around every kernel family: the roofline section's)
     t0 = time.perf_counter()
     for _ in range(steps):
         wl.step()
@@ -360,13 +424,15 @@ def run_config(args, config, n, steps, warmup, rank, world, device, gen, check_r
         ws = wl.batches[0].workspace()
         survivors = int(ws[256:264].view(torch.int64).item())         # queue count (workspace layout, api.cpp)
         dp_reads = int(ws[768:776].view(torch.int64).item()) + int(ws[896:904].view(torch.int64).item())
+    if dump_dir:
+        dump_outputs(wl, dump_dir, rank)
 
     if rank != 0:
         return None
 
     # ---- untimed parity check against the oracle ---------------------------------------------------
     parity = None
-    if check_reads > 0:
+    if full and check_reads > 0:
         ok, parity = wl.parity(check_reads, rank * n)
         if not ok:
             raise SystemExit(f"{config}: parity check against the oracle FAILED: " + parity)
@@ -379,20 +445,6 @@ def run_config(args, config, n, steps, warmup, rank, world, device, gen, check_r
         bytes_per_unit += (8 - (workloads.READ_LEN - (workloads.RAGGED_MIN + workloads.READ_LEN) // 2)) * (2 if spec["kind"] == "paired" else 1)
     total_units = n * world * steps
     value = total_units / elapsed / 1e6
-    # dominant kernel family: the one with the largest share of a step
-    dom = max(step_ms, key=lambda k: step_ms[k])
-    dom_launch_ms = per_launch_ms[dom]
-    reads_per_launch = units_per_launch[dom]        # (the fused multi-adapter path works in chunks of reads)
-    if spec["kind"] == "single":
-        reads_per_launch = {"k_filter": n, "k_back_scan": survivors, "k_dp": dp_reads if dp_reads else survivors,
-                            "k_comparer": n}[dom]
-    per_read_bytes = (178 if spec["kind"] != "multi" else 182) + (workloads.READ_LEN - 150)
-    if ragged:
-        per_read_bytes += 8 - (workloads.READ_LEN - (workloads.RAGGED_MIN + workloads.READ_LEN) // 2)
-    achieved = reads_per_launch * per_read_bytes / (dom_launch_ms * 1e-3) / 1e9 if dom_launch_ms > 0 else 0.0
-    kernel_sum = sum(step_ms.values())
-    step_gbs = n * bytes_per_unit / (kernel_sum * 1e-3) / 1e9 if kernel_sum > 0 else 0.0
-    traffic, valu, profile_note = profile_fields(config, n, dom, dom_launch_ms)
     result = {
         "metric": spec["metric"],
         "value": value,
@@ -428,7 +480,23 @@ def run_config(args, config, n, steps, warmup, rank, world, device, gen, check_r
             "invalid_reads": n_invalid,
             "parity_check": parity,
         },
-        "roofline": {
+    }
+    if full:
+        # dominant kernel family: the one with the largest share of a step
+        dom = max(step_ms, key=lambda k: step_ms[k])
+        dom_launch_ms = per_launch_ms[dom]
+        reads_per_launch = units_per_launch[dom]        # (the fused multi-adapter path works in chunks of reads)
+        if spec["kind"] == "single":
+            reads_per_launch = {"k_filter": n, "k_back_scan": survivors, "k_dp": dp_reads if dp_reads else survivors,
+                                "k_comparer": n}[dom]
+        per_read_bytes = (178 if spec["kind"] != "multi" else 182) + (workloads.READ_LEN - 150)
+        if ragged:
+            per_read_bytes += 8 - (workloads.READ_LEN - (workloads.RAGGED_MIN + workloads.READ_LEN) // 2)
+        achieved = reads_per_launch * per_read_bytes / (dom_launch_ms * 1e-3) / 1e9 if dom_launch_ms > 0 else 0.0
+        kernel_sum = sum(step_ms.values())
+        step_gbs = n * bytes_per_unit / (kernel_sum * 1e-3) / 1e9 if kernel_sum > 0 else 0.0
+        traffic, valu, profile_note = profile_fields(config, n, dom, dom_launch_ms)
+        result["roofline"] = {
             "bound": "hbm",
             "kernel": dom,
             "achieved": achieved,
@@ -452,9 +520,8 @@ def run_config(args, config, n, steps, warmup, rank, world, device, gen, check_r
             "note": "achieved = reads of one launch of the dominant kernel x 178 (182) algorithmic bytes / its HIP-event "
                     "duration; traffic (HBM bytes per launch: FETCH_SIZE x 2 + WRITE_SIZE) and valu (counter-measured "
                     "VALU busy fraction, waves per SIMD, wait fraction) come from the committed rocprofv3 PMC passes",
-        },
-    }
-    if want_cpu:                                       # (rank 0 only: the others returned above)
+        }
+    if full and want_cpu:                                      # (rank 0 only: the others returned above)
         from oracle import cpu_baseline
         try:
             result["cpu_baseline"] = cpu_baseline.run(config, gen, target_seconds=cpu_seconds)
@@ -508,11 +575,12 @@ def main():
     n = args.reads if args.reads is not None else DEFAULT_READS[args.config]
     ragged_mode = "packed" if args.ragged_packed else ("views" if args.ragged else False)
     result = run_config(args, args.config, n, args.steps, args.warmup, rank, world, device, gen, args.check_reads,
-                        args.cpu_seconds, not args.no_cpu_baseline and not ragged_mode, ragged_mode)
+                        args.cpu_seconds, not args.no_cpu_baseline and not ragged_mode, ragged_mode,
+                        full=args.full, dump_dir=args.dump_outputs)
     if rank == 0:
-        # The default invocation (the driver's: C2, one GPU) also carries the other BASELINE configs at their BASELINE
+        # With --full the default invocation (C2, one GPU) also carries the other BASELINE configs at their BASELINE
         # sizes -- a few steps each, with their own parity sample, roofline fraction and a short CPU baseline
-        if (args.config == "C2" and world == 1 and args.reads is None and args.p_adapter is None
+        if (args.full and args.config == "C2" and world == 1 and args.reads is None and args.p_adapter is None
                 and args.read_len is None and not args.no_other_configs and not ragged_mode):
             others = {}
             for cfg in ("C3", "C4", "C5"):

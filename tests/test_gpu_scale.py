@@ -73,7 +73,7 @@ def test_bench_two_ranks_one_json_line(hip):
     box's one device (--oversubscribe: plumbing, not a measurement): rendezvous on 127.0.0.1, contiguous read ranges, gloo
     barriers, max-over-ranks time, ONE JSON line on rank 0 with both ranks' rates, parity, roofline and cpu_baseline"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--oversubscribe", "--reads", "2000000",
-           "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--check-reads", "60000"]
+           "--steps", "2", "--warmup", "1", "--cpu-seconds", "2", "--check-reads", "60000", "--full"]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -99,6 +99,47 @@ def test_bench_two_ranks_one_json_line(hip):
     torch.cuda.synchronize()
     ok, what = wl.parity(60_000, 2_000_000)
     assert ok, what
+
+
+@pytest.mark.parametrize("config,n", [("C2", 600_000), ("C5", 70_000)])
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(hip, tmp_path, config, n):
+    """a run without --full carries the headline figure and the workload, none of the parts that take runs or checks of
+    their own; --dump-outputs writes the arrays of the last timed step (C2: more rows than it writes, so the seeded
+    sample; C5: every row, two result sets) -- compared here with a second, independent pass over the same reads"""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    from cutadapt_amd import workloads
+    args = bench.parse_args(["--config", config, "--reads", str(n), "--steps", "2", "--warmup", "1",
+                             "--dump-outputs", str(tmp_path)])
+    assert args.full is False and args.dump_outputs == str(tmp_path)
+    dev = torch.device("cuda", 0)
+    line = bench.run_config(args, config, n, args.steps, args.warmup, 0, 1, dev, dict(workloads.GEN), args.check_reads,
+                            args.cpu_seconds, True, False, full=args.full, dump_dir=args.dump_outputs)
+    json.dumps(line)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(n / (line["ms_per_step"] * 1e-3) / 1e6, rel=1e-9)
+    assert "roofline" not in line and "cpu_baseline" not in line and line["config"]["parity_check"] is None
+    wl = bench.Workload(config, n, 0, dev, None)
+    wl.step()
+    torch.cuda.synchronize()
+    files = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    rows = files["rows"].astype(np.int64)
+    assert len(rows) == min(n, bench.DUMP_ROWS) and rows[0] == 0 and rows[-1] == n - 1 and (np.diff(rows) > 0).all()
+    assert len(wl.outs) == (2 if config == "C5" else 1)
+    for k, out in enumerate(wl.outs):
+        sfx = "" if k == 0 else f"_{k + 1}"
+        out6, status, best = out.cpu()
+        assert np.array_equal(files["out6" + sfx], out6[rows]) and np.array_equal(files["status" + sfx], status[rows])
+        assert np.array_equal(files["best_adapter" + sfx], np.where(status[rows] == 1, best[rows], -1))
+        assert np.array_equal(files["out6_column_sums" + sfx], out6.sum(0, dtype=np.int64))
+        assert np.array_equal(files["status_counts" + sfx], [(status == v).sum() for v in (0, 1, 2)])
+        assert files["status_counts" + sfx][1] > n // 8                        # (a quarter of the reads carry an adapter)
+    assert len(files) == 1 + 5 * len(wl.outs)
 
 
 _WORKER = r"""
