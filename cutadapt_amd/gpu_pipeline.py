@@ -661,9 +661,10 @@ class _Worker:
             return out
         names = info["names"]
         if getattr(self, "_info_names", None) is not names:
-            blob = "".join(names).encode("ascii")
+            encoded = [x.encode("utf-8") for x in names]            # (offsets in BYTES: a name may hold multi-byte characters)
+            blob = b"".join(encoded)
             off = np.zeros(len(names) + 1, dtype=np.int32)
-            np.cumsum([len(x) for x in names], out=off[1:])
+            np.cumsum([len(x) for x in encoded], out=off[1:])
             self.d_names = torch.from_numpy(np.frombuffer(blob + b"\0", dtype=np.uint8).copy()).to(self.device)
             self.d_name_off = torch.from_numpy(off).to(self.device)
             self.d_info_total = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -682,7 +683,7 @@ class _Worker:
             r6, rst, rbest, n_rounds = rounds_info[0], rounds_info[1], rounds_info[2], int(rounds_info[1].shape[0])
         else:
             r6, rst, rbest, n_rounds = self.res.out6, self.res.status, self.res.best_adapter, 1
-        cap = n_rounds * (n_bytes + n * (max([len(x) for x in names], default=0) + len(suffix) + 48)) + 64
+        cap = n_rounds * (n_bytes + n * (max([len(x.encode("utf-8")) for x in names], default=0) + len(suffix) + 48)) + 64
         if getattr(self, "d_info_out", None) is None or self.d_info_out.numel() < cap:
             self.d_info_out = torch.empty(cap + cap // 4, dtype=torch.uint8, device=self.device)
         _lib.check(L.cah_info_format_device(

@@ -235,10 +235,11 @@ class FastqChunk:
         n = len(self.rec)
         seqs, offsets = self.pack_sequences()
         rows = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 7)
-        blob = "".join(names).encode("ascii")
+        encoded = [x.encode("utf-8") for x in names]                # (offsets in BYTES: a name may hold multi-byte characters)
+        blob = b"".join(encoded)
         name_off = np.zeros(len(names) + 1, dtype=np.int64)
-        np.cumsum([len(x) for x in names], out=name_off[1:])
-        longest = max([len(x) for x in names], default=0)
+        np.cumsum([len(x) for x in encoded], out=name_off[1:])
+        longest = max([len(x) for x in encoded], default=0)
         cap = 3 * int(len(self.buf)) * max(1, 1 + len(rows) // max(n, 1)) + (len(rows) + n) * (96 + longest) + 64
         out = np.empty(cap, dtype=np.uint8)
         out_len = C.c_int64(0)

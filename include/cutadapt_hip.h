@@ -400,7 +400,9 @@ int cah_fastq_span(const uint8_t *buf, int64_t len, int is_final, int64_t max_re
  *                                     packed), d_info[1] = (first bad record + 1) << 8 | code or ~0 (1: no '@',
  *                                     2: no '+', 3: sequence and quality lengths differ)
  *   3. cah_fastq_format_device        "@name\nSEQ[beg:end]\n+\nQUAL[beg:end]\n" of every kept record in record
- *                                     order, d_info[3] = bytes written (<= chunk bytes + 4 * n_records)
+ *                                     order, d_info[3] = bytes written (<= chunk bytes + 4 * n_records); [beg, end) is
+ *                                     cut to the read (beg < 0 -> 0, end > length -> length, end < beg -> empty); a record
+ *                                     that would end behind out_cap is left out, d_info[3] still counts it
  * d_info: int64[8]. */
 size_t cah_fastq_device_scratch_bytes(int64_t chunk_bytes, int64_t max_records);
 int cah_fastq_count_lines_device(const uint8_t *d_buf, int64_t len, void *d_scratch, size_t scratch_bytes,
@@ -459,7 +461,8 @@ int cah_fastq_format_device(const uint8_t *d_buf, const int64_t *d_rec6, int64_t
  * d_mark_end[r]) -- what trimming would have removed; all relative to the read -- become 'N' (mode 1: --action=mask) or lower
  * case, with the characters inside in upper case (mode 2: --action=lowercase; a read without a match has its whole window
  * "inside": the reference upper-cases every read before it looks for adapters, modifiers.py:222-223).  The modifiers behind
- * the adapter step (--poly-a, -l) and cah_fastq_format_device then see the marked read, as the reference's do. */
+ * the adapter step (--poly-a, -l) and cah_fastq_format_device then see the marked read, as the reference's do.
+ * [d_beg, d_end) is cut to the read ([max(beg, 0), min(end, length))); names and qualities are never touched. */
 int cah_mark_reads_device(uint8_t *d_buf, const int64_t *d_rec6, int64_t n_records, const int32_t *d_beg,
                           const int32_t *d_end, const int32_t *d_mark_beg, const int32_t *d_mark_end, int mode,
                           void *stream);
@@ -469,7 +472,9 @@ int cah_mark_reads_device(uint8_t *d_buf, const int64_t *d_rec6, int64_t n_recor
  *   cah_revcomp_in_place_device     turns the records with d_flags[r] != 0 around IN PLACE inside the window the adapter
  *                                   step saw ([d_win_beg[r], + d_win_len[r]) relative to the read; d_win_beg NULL: from
  *                                   0): the sequence becomes its reverse complement (csrc/revcomp.h), the qualities are
- *                                   reversed -- the modifiers behind the adapter step and the formatter see that read;
+ *                                   reversed -- the modifiers behind the adapter step and the formatter see that read
+ *                                   (a window start outside the read is moved to its nearer end, then the window length
+ *                                   is cut to what the read has left behind that start; a length <= 0 turns nothing);
  *   cah_fastq_format_suffix_device  cah_fastq_format_device with `suffix` (suffix_len <= CAH_MAX_NAME_SUFFIX bytes) behind
  *                                   the name of those records (modifiers.py:296-297: `trimmed_read.name += rc_suffix`);
  *                                   out_cap >= chunk length + (4 + suffix_len) * n_records always suffices. */
@@ -497,7 +502,11 @@ int cah_fastq_format_suffix_device(const uint8_t *d_buf, const int64_t *d_rec6, 
  *     --revcomp), "0" or "1" (RC_MAP, steps.py:224), and the names of the reads with d_is_rc[r] != 0 carry `suffix`;
  *   a read without a match:  name TAB -1 TAB seq[fb:fe] TAB qual[fb:fe] LF   with [fb, fe) = [d_final_beg[r], d_final_end[r]):
  *     the read as it is written (steps.py:248-251).
- * d_names / d_name_off (int32[n_names + 1]): the adapters' names back to back in plan order (device memory).  d_scratch as
+ * Values the matcher never produces are made safe, not trusted: rstop is cut to [0, length of the read at that round] and
+ * rstart to [0, rstop] (the row prints the cut values); a d_best outside [0, n_names) counts as adapter 0; with n_names == 0
+ * the adapter column is empty; [fb, fe) is cut to the read as the formatter cuts [beg, end).
+ * d_names / d_name_off (int32[n_names + 1]): the adapters' names back to back in plan order (device memory; bytes: a name may
+ * be UTF-8).  d_scratch as
  * for cah_fastq_format_device (called after it: the formatter's arrays are reused).
  * out_cap >= rounds * (chunk length + n_records * (longest adapter name + suffix_len + 48)) always suffices. */
 int cah_info_format_device(const uint8_t *d_buf, const int64_t *d_rec6, int64_t n_records, const int32_t *d_out6,
