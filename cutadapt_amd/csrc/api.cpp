@@ -1913,7 +1913,8 @@ int cah_linked_match_batch_uniform(const cah_plan* front_plan, const cah_plan* b
 
 int cah_validate_ascii_batch(const uint8_t* d_seqs, const int64_t* d_offsets, const int32_t* d_lens,
                              int64_t n_reads, int32_t* d_bad, void* stream) {
-    if (!d_bad) return fail(CAH_EINVAL, "d_bad is NULL");
+    if (!d_bad) return fail(CAH_EINVAL, "cah_validate_ascii_batch: d_bad is NULL");
+    if (n_reads > 0 && !d_offsets) return fail(CAH_EINVAL, "cah_validate_ascii_batch: NULL argument");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int32_t), s));
     if (n_reads <= 0) return CAH_OK;

@@ -317,7 +317,7 @@ extern "C" {
 
 int cah_quality_trim_batch(const uint8_t* d_quals, const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads,
                            int32_t cutoff_front, int32_t cutoff_back, int32_t base, int32_t* d_start_stop, void* stream) {
-    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "n_reads < 0");
+    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "cah_quality_trim_batch: n_reads < 0");
     if (n_reads == 0) return CAH_OK;
     if (!d_offsets || !d_start_stop) return cah_set_error_(CAH_EINVAL, "cah_quality_trim_batch: NULL argument");
     hipLaunchKernelGGL(k_quality_trim, dim3(blocks_for(n_reads)), dim3(256), 0, (hipStream_t)stream, d_quals, d_offsets,
@@ -328,7 +328,7 @@ int cah_quality_trim_batch(const uint8_t* d_quals, const int64_t* d_offsets, con
 
 int cah_nextseq_trim_batch(const uint8_t* d_seqs, const uint8_t* d_quals, const int64_t* d_offsets, const int32_t* d_lens,
                            int64_t n_reads, int32_t cutoff, int32_t base, int32_t* d_stop, void* stream) {
-    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "n_reads < 0");
+    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "cah_nextseq_trim_batch: n_reads < 0");
     if (n_reads == 0) return CAH_OK;
     if (!d_offsets || !d_stop) return cah_set_error_(CAH_EINVAL, "cah_nextseq_trim_batch: NULL argument");
     hipLaunchKernelGGL(k_nextseq_trim, dim3(blocks_for(n_reads)), dim3(256), 0, (hipStream_t)stream, d_seqs, d_quals,
@@ -342,7 +342,7 @@ int cah_nextseq_trim_batch(const uint8_t* d_seqs, const uint8_t* d_quals, const 
 int cah_nextseq_trim_batch_q(const uint8_t* d_seqs, const uint8_t* d_quals, const int64_t* d_offsets,
                              const int64_t* d_qual_offsets, const int32_t* d_lens, int64_t n_reads, int32_t cutoff,
                              int32_t base, int32_t* d_stop, void* stream) {
-    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "n_reads < 0");
+    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "cah_nextseq_trim_batch_q: n_reads < 0");
     if (n_reads == 0) return CAH_OK;
     if (!d_offsets || !d_qual_offsets || !d_lens || !d_stop)
         return cah_set_error_(CAH_EINVAL, "cah_nextseq_trim_batch_q: NULL argument");
@@ -354,7 +354,7 @@ int cah_nextseq_trim_batch_q(const uint8_t* d_seqs, const uint8_t* d_quals, cons
 
 int cah_poly_a_trim_batch(const uint8_t* d_seqs, const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads,
                           int32_t revcomp, int32_t* d_index, void* stream) {
-    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "n_reads < 0");
+    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "cah_poly_a_trim_batch: n_reads < 0");
     if (n_reads == 0) return CAH_OK;
     if (!d_offsets || !d_index) return cah_set_error_(CAH_EINVAL, "cah_poly_a_trim_batch: NULL argument");
     hipLaunchKernelGGL(k_poly_a_trim, dim3(blocks_for(n_reads)), dim3(256), 0, (hipStream_t)stream, d_seqs, d_offsets,
@@ -365,8 +365,10 @@ int cah_poly_a_trim_batch(const uint8_t* d_seqs, const int64_t* d_offsets, const
 
 int cah_expected_errors_batch(const uint8_t* d_quals, const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads,
                               int32_t base, double* d_expected, uint8_t* d_status, void* stream) {
-    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "n_reads < 0");
-    if (base < 0 || base > 126) return cah_set_error_(CAH_EINVAL, "quality base out of range");
+    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "cah_expected_errors_batch: n_reads < 0");
+    // the table has the reference's 94 entries (phred 0 .. 93): a base below 33 would let a valid byte index past it
+    if (base < 33 || base > 126)
+        return cah_set_error_(CAH_EINVAL, "cah_expected_errors_batch: quality base out of range (33..126)");
     if (n_reads == 0) return CAH_OK;
     if (!d_offsets || !d_expected) return cah_set_error_(CAH_EINVAL, "cah_expected_errors_batch: NULL argument");
     const double* tab = nullptr;
@@ -408,7 +410,7 @@ static int reverse_reads_impl(const char* who, const uint8_t* d_seqs, const int6
 int cah_linked_views(const int32_t* d_out6_front, const uint8_t* d_status_front, const int64_t* d_offsets,
                      const int32_t* d_lens, int32_t read_len, int64_t n_reads, int64_t* d_starts, int32_t* d_view_lens,
                      void* stream) {
-    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "n_reads < 0");
+    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "cah_linked_views: n_reads < 0");
     if (n_reads == 0) return CAH_OK;
     if (!d_out6_front || !d_status_front || !d_starts || !d_view_lens || (read_len <= 0 && !d_offsets))
         return cah_set_error_(CAH_EINVAL, "cah_linked_views: NULL argument");

@@ -225,7 +225,10 @@ int cah_set_deferred_errors(int on);
 
 /* The views the second stage of a linked adapter searches (adapters.py:1222-1224): d_starts[r] = start of read r +
  * (front match ? its query_stop : 0), d_view_lens[r] = what is left of the read.  Reads as in cah_match_batch, or
- * read_len > 0: equally long reads back to back from byte 0 (d_offsets may be NULL). */
+ * read_len > 0: equally long reads back to back from byte 0 (d_offsets may be NULL).  Only d_status_front[r] ==
+ * CAH_MATCH counts as a front match (CAH_INVALID does not); query_stop (d_out6_front[6r + 3]) is clamped into
+ * [0, n_r], n_r the read's length, so a view never starts in front of its read or ends behind it.  Rows >= n_reads of
+ * the outputs are not written. */
 int cah_linked_views(const int32_t *d_out6_front, const uint8_t *d_status_front, const int64_t *d_offsets,
                      const int32_t *d_lens, int32_t read_len, int64_t n_reads, int64_t *d_starts,
                      int32_t *d_view_lens, void *stream);
@@ -254,8 +257,9 @@ size_t cah_workspace_bytes(int64_t n_reads);
  * least this value and otherwise matches one adapter after the other (same results). */
 size_t cah_plan_workspace_bytes(const cah_plan *plan, int64_t n_reads);
 
-/* d_bad[0] (int32) is set to the number of reads holding a byte >= 0x80 (the reference
- * rejects such strings up front, _align.pyx:44-45 / _kmer_finder.pyx:182-183). */
+/* d_bad[0] (int32) is set to the number of READS (not bytes) holding a byte >= 0x80 inside their window (the reference
+ * rejects such strings up front, _align.pyx:44-45 / _kmer_finder.pyx:182-183).  d_bad is reset on every call,
+ * n_reads <= 0 included. */
 int cah_validate_ascii_batch(const uint8_t *d_seqs, const int64_t *d_offsets,
                              const int32_t *d_lens, int64_t n_reads, int32_t *d_bad,
                              void *stream);
@@ -584,7 +588,18 @@ int cah_revcomp_reads_batch(const uint8_t *d_seqs, const int64_t *d_offsets, con
  *   cah_poly_a_trim_batch    poly_a_trim_index (:116-165)             -> d_index int32[n]
  *   cah_expected_errors_batch expected_errors (:168-190, expected_errors.h:103-140) -> double[n],
  *                            bit-identical (same accumulation order); an invalid phred value gives
- *                            -1.0 and d_status[r] = CAH_INVALID (the reference raises ValueError). */
+ *                            -1.0 and d_status[r] = CAH_INVALID (the reference raises ValueError).
+ *                            d_status may be NULL.  base must be 33 .. 126 (CAH_EINVAL otherwise): the
+ *                            table holds the reference's 94 entries, phred 0 .. 93, and a smaller base
+ *                            would let a valid byte index past it.
+ * What all of them guarantee (tests/test_gpu_qualtrim_kernels.py holds them to it):
+ *   - the result of read r depends only on the bytes [offset_r, offset_r + len_r) of its buffers; whatever
+ *     lies between the reads, in front of the first or behind the last, is never looked at;
+ *   - only rows < n_reads of the outputs are written; n_reads == 0 touches nothing;
+ *   - quality bytes are interpreted as C's signed `char`, as the reference does (a byte >= 0x80 is a
+ *     negative quality); cah_expected_errors_batch alone reads them unsigned, like expected_errors.h;
+ *   - d_lens[r] >= 0 is the caller's duty: a negative length is not checked for;
+ *   - offsets are 64-bit: a buffer may be larger than 4 GiB. */
 int cah_quality_trim_batch(const uint8_t *d_quals, const int64_t *d_offsets, const int32_t *d_lens,
                            int64_t n_reads, int32_t cutoff_front, int32_t cutoff_back,
                            int32_t base, int32_t *d_start_stop, void *stream);
