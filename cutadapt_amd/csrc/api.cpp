@@ -200,6 +200,11 @@ struct MultiPlan {
     std::vector<uint32_t> bitmap;
     std::vector<uint64_t> scan_tab, row_tab;
     M2Tables m2;                          // the streaming form's tables (m2.hdr.ok: equally long short reads take it)
+    // The MIXED form (build_multi_mixed): adapters of different lengths.  hdr.ok stays 0 -- the older fused kernels are
+    // one-shape --, m2 holds m2_build_mixed's tables, scan_tab / row_tab are filled; a batch the streaming form cannot
+    // take goes through the per-adapter loop
+    bool mixed = false;
+    int longest = 0;                      // the (first) longest adapter: word form, ROWS and thr_last come from it
     MultiPlan() { memset(&hdr, 0, sizeof(hdr)); memset(&m2.hdr, 0, sizeof(m2.hdr)); }
 };
 
@@ -253,15 +258,17 @@ static int plan_on_device(const cah_plan* plan, const PlanDeviceCopy** out) {
             HIP_TRY(hipMemcpy(ld.d_ncnt, lt.ncnt.data(), sizeof(int32_t) * lt.ncnt.size(), hipMemcpyHostToDevice));
         }
         const MultiPlan& mp = plan->multi;
-        if (mp.hdr.ok) {
+        if (mp.hdr.ok || mp.mixed) {
 #define CAH_UPLOAD(dst, vec)                                                                              \
             HIP_TRY(hipMalloc((void**)&(dst), sizeof((vec)[0]) * std::max<size_t>((vec).size(), 1)));      \
             if (!(vec).empty()) HIP_TRY(hipMemcpy((dst), (vec).data(), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc((void**)&dc.d_mhdr, sizeof(CahMultiHeader)));
-            HIP_TRY(hipMemcpy(dc.d_mhdr, &mp.hdr, sizeof(CahMultiHeader), hipMemcpyHostToDevice));
-            CAH_UPLOAD(dc.d_mdir, mp.dir)
-            CAH_UPLOAD(dc.d_mentries, mp.entries)
-            CAH_UPLOAD(dc.d_mbitmap, mp.bitmap)
+            if (mp.hdr.ok) {
+                HIP_TRY(hipMalloc((void**)&dc.d_mhdr, sizeof(CahMultiHeader)));
+                HIP_TRY(hipMemcpy(dc.d_mhdr, &mp.hdr, sizeof(CahMultiHeader), hipMemcpyHostToDevice));
+                CAH_UPLOAD(dc.d_mdir, mp.dir)
+                CAH_UPLOAD(dc.d_mentries, mp.entries)
+                CAH_UPLOAD(dc.d_mbitmap, mp.bitmap)
+            }
             CAH_UPLOAD(dc.d_mscan, mp.scan_tab)
             CAH_UPLOAD(dc.d_mrow, mp.row_tab)
             if (mp.m2.hdr.ok) {
@@ -694,10 +701,87 @@ static int build_matcher(const cah_adapter_desc& d, int index, CahMatcher& mt,
 // k-mer set is a whole-read set (0, None) or a tail set (-L, None) of ACGT k-mers of 1..32 characters
 // matched without wildcards: exactly what `-a file:` with equally long adapters gives (BASELINE C4).
 // Anything else keeps the one-adapter-at-a-time loop.  CAH_NO_MULTI=1 disables it (A/B, parity tests).
+// per-adapter match tables indexed by (read character & 31): only A/C/G/T (either case) match anything
+static void fill_multi_tabs(const cah_plan* plan, int n, MultiPlan& mp) {
+    mp.scan_tab.assign((size_t)n * CAH_MULTI_TAB_STRIDE, 0);
+    mp.row_tab.assign((size_t)n * CAH_MULTI_TAB_STRIDE, 0);
+    for (int a = 0; a < n; a++) {
+        const CahMatcher& mt = plan->matchers[(size_t)a];
+        for (int i = 0; i < CAH_MULTI_TAB; i++) {
+            const bool letter = i == 1 || i == 3 || i == 7 || i == 20;                 // A C G T
+            const int ch = 64 + i;
+            mp.scan_tab[(size_t)a * CAH_MULTI_TAB_STRIDE + i] = letter ? mt.scanmask[ch] : mt.scanmask[0];
+            mp.row_tab[(size_t)a * CAH_MULTI_TAB_STRIDE + i] = letter ? mt.rowmask[ch] : 0ull;
+        }
+    }
+}
+
+// the reference search sets of every adapter as m2_build takes them
+static void m2_ref_sets(const cah_adapter_desc* descs, int n, std::vector<std::string>& ads, std::vector<std::vector<M2RefKmer>>& ref) {
+    ref.assign((size_t)n, std::vector<M2RefKmer>());
+    for (int a = 0; a < n; a++) {
+        ads.push_back(std::string(descs[a].sequence, (size_t)descs[a].length));
+        for (int si = 0; si < descs[a].n_kmer_sets; si++) {
+            const cah_kmer_set& ks = descs[a].kmer_sets[si];
+            for (int t = 0; t < ks.n_kmers; t++)
+                ref[(size_t)a].push_back({std::string(ks.kmers[t]), ks.start == 0 ? CAH_M2_WHOLE : (int)-ks.start});
+        }
+    }
+}
+
+// The MIXED form of the streaming multi-adapter path: 8..128 plain-ACGT 3' adapters of DIFFERENT lengths that are all
+// scan-eligible with kacc == k, share one min_overlap and agree on thr[] and, row by row, on thr_last[] -- one
+// max_error_rate: what `-a file:` gives the adapters of a real FASTA (TruSeq 33 / 34, Nextera 19, small RNA 21 ...).
+// A plan built from absolute max_errors has another rate per length and stays on the per-adapter loop.  There is no
+// older fused form behind it (multi.hip is one-shape): batches the streaming form does not take (reads over 160
+// characters, a ragged packed batch without frames) go through the loop as before.  The form needs 8 adapters
+// whatever CAH_MULTI_MIN says (CAH_MULTI_MIXED_MIN >= 2 lowers that for experiments); CAH_NO_MULTI_MIXED=1, CAH_NO_MULTI=1
+// and CAH_NO_MULTI2=1 turn it off.
+static void build_multi_mixed(const cah_adapter_desc* descs, int n, cah_plan* plan) {
+    MultiPlan& mp = plan->multi;
+    if (env_flag_early("CAH_NO_MULTI_MIXED") || env_flag_early("CAH_NO_MULTI2")) return;
+    int min_adapters = 8;
+    if (const char* e = getenv("CAH_MULTI_MIXED_MIN")) { const int v = atoi(e); if (v >= 2) min_adapters = v; }
+    if (n < min_adapters || n > CAH_MULTI_MAX_ADAPTERS || n > 128) return;
+    int longest = 0;
+    for (int a = 1; a < n; a++) if (plan->matchers[(size_t)a].m > plan->matchers[(size_t)longest].m) longest = a;
+    const CahMatcher& ml = plan->matchers[(size_t)longest];
+    std::vector<int> k_of((size_t)n);
+    for (int a = 0; a < n; a++) {
+        const cah_adapter_desc& d = descs[a];
+        const CahMatcher& mt = plan->matchers[(size_t)a];
+        if (d.kind != CAH_KIND_ALIGNER || !mt.scan_ok || d.wildcard_ref || d.wildcard_query) return;
+        if (mt.m < 1 || mt.m > CAH_MAX_M || mt.kacc != mt.k || mt.min_overlap != ml.min_overlap) return;
+        if (memcmp(mt.thr, ml.thr, sizeof(mt.thr)) != 0) return;
+        for (int i = 0; i <= mt.m; i++) if (mt.thr_last[i] != ml.thr_last[i]) return;
+        for (int i = 0; i < mt.m; i++) { const char c = d.sequence[i]; if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return; }
+        if (d.n_kmer_sets <= 0 || !d.kmer_sets || d.kmer_ref_wildcards || d.kmer_query_wildcards) return;
+        for (int si = 0; si < d.n_kmer_sets; si++) {
+            const cah_kmer_set& ks = d.kmer_sets[si];
+            if (!((ks.start == 0 && ks.stop == 0) || (ks.start < 0 && ks.stop == 0 && ks.start >= -255))) return;
+            for (int t = 0; t < ks.n_kmers; t++) if (!ks.kmers[t] || !*ks.kmers[t]) return;
+        }
+        k_of[(size_t)a] = mt.kacc;
+    }
+    std::vector<std::string> ads;
+    std::vector<std::vector<M2RefKmer>> ref;
+    m2_ref_sets(descs, n, ads, ref);
+    if (!m2_build_mixed(ads, ml.thr_last, k_of.data(), ml.min_overlap, ref, mp.m2) || !mp.m2.hdr.mixed) {
+        memset(&mp.m2.hdr, 0, sizeof(mp.m2.hdr));
+        return;
+    }
+    fill_multi_tabs(plan, n, mp);
+    mp.mixed = true;
+    mp.longest = longest;
+}
+
 static void build_multi(const cah_adapter_desc* descs, int n, cah_plan* plan) {
     MultiPlan& mp = plan->multi;
     const char* off = getenv("CAH_NO_MULTI");
     if (off && *off && *off != '0') return;
+    // adapters that differ in shape by their LENGTH: the mixed form, or the per-adapter loop
+    for (int a = 1; a < n; a++)
+        if (plan->matchers[(size_t)a].m != plan->matchers[0].m) { build_multi_mixed(descs, n, plan); return; }
     // below ~8 adapters one lean prefilter pass per adapter is faster than the fused pass (measured on C5:
     // 2 adapters, 2 x 9.9 ms against 75 ms per 125 M reads); CAH_MULTI_MIN overrides the threshold
     int min_adapters = 8;
@@ -780,33 +864,15 @@ static void build_multi(const cah_adapter_desc* descs, int n, cah_plan* plan) {
         mp.entries.push_back(en);
     }
     h.n_entries = (uint32_t)mp.entries.size();
-    // per-adapter match tables indexed by (read character & 31): only A/C/G/T (either case) match anything
-    mp.scan_tab.assign((size_t)n * CAH_MULTI_TAB_STRIDE, 0);
-    mp.row_tab.assign((size_t)n * CAH_MULTI_TAB_STRIDE, 0);
-    for (int a = 0; a < n; a++) {
-        const CahMatcher& mt = plan->matchers[(size_t)a];
-        for (int i = 0; i < CAH_MULTI_TAB; i++) {
-            const bool letter = i == 1 || i == 3 || i == 7 || i == 20;                 // A C G T
-            const int ch = 64 + i;
-            mp.scan_tab[(size_t)a * CAH_MULTI_TAB_STRIDE + i] = letter ? mt.scanmask[ch] : mt.scanmask[0];
-            mp.row_tab[(size_t)a * CAH_MULTI_TAB_STRIDE + i] = letter ? mt.rowmask[ch] : 0ull;
-        }
-    }
+    fill_multi_tabs(plan, n, mp);
     h.ok = 1;
     // the streaming form (multi2.h): the same plan as tables of REF + WIDE k-mers of up to ten characters.
     // CAH_NO_MULTI2=1 keeps the older kernels (A/B, parity tests)
     const char* off2 = getenv("CAH_NO_MULTI2");
     if (!(off2 && *off2 && *off2 != '0')) {
         std::vector<std::string> ads;
-        std::vector<std::vector<M2RefKmer>> ref((size_t)n);
-        for (int a = 0; a < n; a++) {
-            ads.push_back(std::string(descs[a].sequence, (size_t)descs[a].length));
-            for (int si = 0; si < descs[a].n_kmer_sets; si++) {
-                const cah_kmer_set& ks = descs[a].kmer_sets[si];
-                for (int t = 0; t < ks.n_kmers; t++)
-                    ref[(size_t)a].push_back({std::string(ks.kmers[t]), ks.start == 0 ? CAH_M2_WHOLE : (int)-ks.start});
-            }
-        }
+        std::vector<std::vector<M2RefKmer>> ref;
+        m2_ref_sets(descs, n, ads, ref);
         if (!m2_build(ads, m0.thr_last, m0.kacc, m0.k, m0.min_overlap, ref, mp.m2)) memset(&mp.m2.hdr, 0, sizeof(mp.m2.hdr));
     }
 }
@@ -951,6 +1017,11 @@ int cah_plan_prefilter_kind(const cah_plan* plan, int32_t adapter, int32_t* out)
 int cah_plan_multi_kind(const cah_plan* plan, int32_t read_len, int32_t* out) {
     if (!plan || !out) return fail(CAH_EINVAL, "plan or out is NULL");
     const MultiPlan& mp = plan->multi;
+    if (mp.mixed) {                                          // (no fused form behind the mixed one)
+        *out = (multi2_read_len_ok(mp.m2.hdr, read_len) && !env_flag_early("CAH_NO_MULTI2") && !env_flag_early("CAH_NO_MULTI_MIXED") &&
+                !env_flag_early("CAH_NO_MULTI")) ? CAH_MULTI_STREAM : CAH_MULTI_SEQUENTIAL;
+        return CAH_OK;
+    }
     *out = !mp.hdr.ok ? CAH_MULTI_SEQUENTIAL
                       : ((mp.m2.hdr.ok && multi2_read_len_ok(mp.m2.hdr, read_len) && !env_flag_early("CAH_NO_MULTI2")) ? CAH_MULTI_STREAM : CAH_MULTI_FUSED);
     return CAH_OK;
@@ -1132,7 +1203,7 @@ static size_t long_scratch_bytes(const cah_plan* plan, int64_t lanes) {
 size_t cah_plan_workspace_bytes(const cah_plan* plan, int64_t n_reads) {
     if (n_reads < 0) n_reads = 0;
     size_t need = cah_workspace_bytes(n_reads);
-    if (plan && plan->multi.hdr.ok)
+    if (plan && (plan->multi.hdr.ok || plan->multi.mixed))
         need += ws_key_bytes(n_reads) + (size_t)multi_pair_cap(plan, n_reads) * 20 + 2 * ws_keys_bytes(n_reads) + 256;
     if (plan && plan->max_long_m > 0) need += long_scratch_bytes(plan, long_scratch_lanes(n_reads, 256)) + 256;
     return need;
@@ -1479,6 +1550,16 @@ int cah_last_multi_path(void) { return t_last_multi_path; }
 static thread_local int t_deferred_errors = 0;
 int cah_set_deferred_errors(int on) { const int old = t_deferred_errors; t_deferred_errors = on ? 1 : 0; return old; }
 
+// Does the streaming form (multi2.hip) take this batch of this plan?  Equally long reads (no lengths array), or views /
+// frames of such a length (ul.inner: d_offsets / d_lens are the views' starts and lengths), of a length the plan's tables
+// allow.  ONE predicate for match_batch_multi_once, which streams or falls to the fused kernels by it, and for
+// match_batch_impl, which sends a MIXED plan -- no fused kernels behind it -- to the per-adapter loop where it is false.
+static bool multi_streams(const MultiPlan& mp, const UniformLayout& ul, const int64_t* d_offsets, const int32_t* d_lens) {
+    const bool views = ul.inner && d_lens != nullptr && d_offsets != nullptr;
+    return mp.m2.hdr.ok && ul.len > 0 && (!d_lens || (views && !env_flag("CAH_NO_MULTI2_VIEWS"))) &&
+           multi2_read_len_ok(mp.m2.hdr, ul.len) && !env_flag("CAH_NO_MULTI2");
+}
+
 static thread_local bool t_m2_waited_in_vain = false;     // the last failure of match_batch_multi_once was err bit 1 alone
 static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd, const uint8_t* d_seqs,
                                   const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads, int32_t* d_out6,
@@ -1518,9 +1599,11 @@ static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd
     // class each (the suffix compare of the error-free rows happens there), k_multi_scan scans them page by page.
     t_last_multi_path = CAH_MULTI_FUSED;
     const bool views = ul.inner && d_lens != nullptr && d_offsets != nullptr;    // views inside the reads of a uniform batch
-    if (mp.m2.hdr.ok && ul.len > 0 && (!d_lens || (views && !env_flag("CAH_NO_MULTI2_VIEWS"))) &&
-        multi2_read_len_ok(mp.m2.hdr, ul.len) && !env_flag("CAH_NO_MULTI2")) {
+    if (multi_streams(mp, ul, d_offsets, d_lens)) {
         t_last_multi_path = CAH_MULTI_STREAM;
+        // (a mixed plan: every pair with its own adapter's length; word form, ROWS and thr_last from the longest -- the
+        // explicit-row forms of 33 / 34 characters have no pad rows for a shorter adapter: the 64-bit form serves)
+        const CahMatcher& mlong = plan->matchers[(size_t)(mp.mixed ? mp.longest : 0)];
         // the pool: pages of CAH_M2_PAGE pairs + one header word each, inside the pair area
         const int64_t max_pages = ((int64_t)cap * 8) / (CAH_M2_PAGE * 8 + 4);
         uint32_t* d_page_hdr = (uint32_t*)(d_pairs + max_pages * CAH_M2_PAGE);
@@ -1590,6 +1673,7 @@ static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd
                 Multi2ScanArgs sa;
                 sa.uniform_first = ul.first; sa.uniform_len = ul.len;
                 sa.kind = scan_word_kind(m0.m);
+                if (mp.mixed) { sa.mixed = 1; sa.longest = mp.longest; sa.kind = scan_word_kind(mlong.m) == 1 ? 1 : 0; }
                 sa.rows_lo = mp.m2.hdr.rows_lo;
                 sa.matcher = pd->d_matchers; sa.tab = pd->d_mscan; sa.n_adapters = (int32_t)A;
                 sa.seqs = d_seqs; sa.pairs = d_pairs; sa.page_hdr = d_page_hdr;
@@ -1618,7 +1702,7 @@ static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd
                 a.win = d_win; a.queue_cap = cap; a.work_counter = counters + WS_DPWORK;
                 a.m2_hdr = pd->d_m2hdr; a.m2_ref_begin = pd->d_m2refbegin; a.m2_ref_list = pd->d_m2reflist;
                 ProfScope ps(s, CAH_PROF_DP, round ? -1 : cnt);
-                HIP_TRY(launch_dp(a, m0.m, true, true, std::min(cap, cnt * A), pd->n_cus, s));
+                HIP_TRY(launch_dp(a, mlong.m, true, true, std::min(cap, cnt * A), pd->n_cus, s, mp.mixed));
             }
           }
         }
@@ -1627,6 +1711,7 @@ static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd
                                     deferred ? counters + WS_M2_ERR : nullptr));
         return CAH_OK;
     }
+    if (mp.mixed) return fail(CAH_EINTERNAL, "multi-adapter path: a mixed plan has no fused form for this batch");
     // (the older kernels take views through their starts and lengths alone)
     const UniformLayout ulo = ul.inner ? UniformLayout() : ul;
     for (int64_t lo = 0; lo < n_reads; lo += chunk) {
@@ -1703,7 +1788,14 @@ static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const i
     // (cah_match_batch_frames: views anywhere in the buffer with a frame length -- only the streaming multi-adapter form
     // has a use for the frame; every other path takes them as the plain views they are)
     // (... a single adapter's streaming prefilter likewise, adapter by adapter: run_filter)
-    const bool multi_form = plan->multi.hdr.ok && workspace_bytes >= cah_plan_workspace_bytes(plan, n_reads);
+    const bool ws_multi = workspace_bytes >= cah_plan_workspace_bytes(plan, n_reads);
+    const bool multi_form = plan->multi.hdr.ok && ws_multi;
+    // A MIXED plan (build_multi_mixed) takes the multi-adapter path only where match_batch_multi_once streams: equally
+    // long reads of 16..160 characters, or views / frames of such a length; anything else is the per-adapter loop below
+    // (the layout match_batch_multi gets below: views keep theirs, a suffix-only layout is no uniform batch for it)
+    const UniformLayout ul_multi = (ul_in.inner && d_lens) ? ul_in : (ul_in.suffix ? UniformLayout() : ul_in);
+    const bool mixed_go = plan->multi.mixed && ws_multi && multi_streams(plan->multi, ul_multi, (const int64_t*)d_offsets, d_lens) &&
+                          !env_flag("CAH_NO_MULTI_MIXED") && !env_flag("CAH_NO_MULTI");
     const UniformLayout ul = (ul_in.general && multi_form &&
                               !(plan->multi.m2.hdr.ok && multi2_read_len_ok(plan->multi.m2.hdr, ul_in.len) && !env_flag("CAH_NO_MULTI2") &&
                                 !env_flag("CAH_NO_MULTI2_VIEWS")))
@@ -1713,7 +1805,7 @@ static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const i
     const UniformLayout ul_rest = ul.suffix ? UniformLayout() : ul;     // what every kernel but the prefilter sees
     // The result rows are zeroed by the first adapter's prefilter on its way through the batch when there is one
     // (FilterArgs::clear_out6: 24 B per read that would otherwise be a memset pass of its own), by a memset if not.
-    const bool multi_path = plan->multi.hdr.ok && workspace_bytes >= cah_plan_workspace_bytes(plan, n_reads);
+    const bool multi_path = multi_form || mixed_go;
     int32_t first_aligner = -1;
     for (int32_t ad = 0; ad < (int32_t)plan->matchers.size() && first_aligner < 0; ad++)
         if (plan->matchers[(size_t)ad].kind != CAH_KIND_KMER_ONLY) first_aligner = ad;
@@ -1744,7 +1836,7 @@ static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const i
         }
     }
     t_last_multi_path = CAH_MULTI_SEQUENTIAL;
-    if (plan->multi.hdr.ok && workspace_bytes >= cah_plan_workspace_bytes(plan, n_reads))
+    if (multi_path)
         // (views inside the reads of a uniform batch -- ul.inner: d_offsets / d_lens are the views' starts and lengths -- go
         // through with their layout: the streaming form takes them end-aligned, multi2.hip's RV form)
         return match_batch_multi(plan, pd, d_seqs, d_offsets, d_lens, n_reads, d_out6, d_best_adapter, d_status, ws,

@@ -91,6 +91,8 @@ struct DpArgs {
     const int32_t* m2_ref_begin = nullptr;
     const uint32_t* m2_ref_list = nullptr;
 };
+// launch_dp's ROWS of a mixed multi-adapter plan (k_dp_packed<ROWS, true, true>: fewer sizes than the one-shape kernels have)
+inline int dp_mixed_rows(int m) { return m <= 24 ? 24 : (m <= 32 ? 32 : (m <= 48 ? 48 : 64)); }
 
 #define CAH_MULTI_TAB_STRIDE 33   // 32 entries + 1 of padding: spreads the adapters' tables over the LDS banks
 
@@ -189,8 +191,9 @@ bool stream2_class_ok(int n_lead, int n_tw);
 hipError_t launch_uniform_check(const int64_t* offsets, int64_t n_reads, int64_t max_read_len, unsigned long long* flag,
                                 int n_cus, hipStream_t s);
 hipError_t launch_filter(const FilterArgs& a, int mode, bool narrow_words, int n_cus, hipStream_t s);
+// mixed: the pairs' adapters differ in length (m: the longest) -- every lane reads m and k of its pair's matcher
 hipError_t launch_dp(const DpArgs& a, int m, bool unit_indel_cost, bool back_adapter, int64_t max_items, int n_cus,
-                     hipStream_t s);
+                     hipStream_t s, bool mixed = false);
 hipError_t launch_back_scan(const ScanArgs& a, int64_t max_items, int n_cus, hipStream_t s);
 
 // multi.hip: the fused multi-adapter prefilter and the final decode of the per-read best keys
@@ -283,6 +286,10 @@ struct Multi2ScanArgs {
     const int64_t* view_starts = nullptr;
     const int32_t* view_lens = nullptr;
     int32_t view_general = 0;        // (Multi2Args::view_general)
+    // mixed form (m2_build_mixed): the adapters differ in length -- every pair takes m and k from matcher[its adapter],
+    // thr_last from matcher[longest]; kind is 0 or 1
+    int32_t mixed = 0;
+    int32_t longest = 0;
 };
 bool multi2_read_len_ok(const CahMulti2Header& h, int read_len);
 size_t multi2_lds_bytes(const CahMulti2Header& h);

@@ -1409,7 +1409,8 @@ __device__ __forceinline__ unsigned dpp_select(const dpp_pred p, const unsigned 
 }
 #endif
 
-template <int I, int ROWS>
+// ANYM: the lanes' adapters differ in length (the mixed multi-adapter form): cell (m, j) is captured at every row
+template <int I, int ROWS, bool ANYM = false>
 __device__ __forceinline__ void dp_rows_packed(unsigned (&w)[ROWS + 1], const unsigned mk_lo, const unsigned mk_hi,
                                                unsigned wd, int& nl, unsigned& cm_w, const int last, const int m,
                                                const unsigned klim, const dpp_pred eq, const bool in_band) {
@@ -1430,7 +1431,9 @@ __device__ __forceinline__ void dp_rows_packed(unsigned (&w)[ROWS + 1], const un
         const unsigned e = wd + PK_D_MATCH;
         const unsigned wn = dpp_select(eq, e, mn);
         w[I] = in_band ? wn : wold;                       // out of band: the stale cell stays
-        if constexpr (I > ROWS - 8) {
+        if constexpr (ANYM) {
+            cm_w = I == m ? wn : cm_w;
+        } else if constexpr (I > ROWS - 8) {
             if (I == m) cm_w = wn;                        // wave-uniform capture of cell (m, j)
         }
         const unsigned mword = I < 32 ? mk_lo : mk_hi;    // predicates of row I + 1
@@ -1447,7 +1450,7 @@ __device__ __forceinline__ void dp_rows_packed(unsigned (&w)[ROWS + 1], const un
         nl = (int)__builtin_amdgcn_bitop3_b32(okm, (unsigned)I, (unsigned)nl, 0xCA);
 #endif
         if constexpr ((I % CAH_SCHED_ROWS) == 0) __builtin_amdgcn_sched_barrier(0);
-        dp_rows_packed<I + 1, ROWS>(w, mk_lo, mk_hi, wold, nl, cm_w, last, m, klim, eq_next, band_next);
+        dp_rows_packed<I + 1, ROWS, ANYM>(w, mk_lo, mk_hi, wold, nl, cm_w, last, m, klim, eq_next, band_next);
     }
 }
 
@@ -1477,7 +1480,9 @@ __device__ __forceinline__ unsigned get_row_packed(const unsigned (&w)[ROWS + 1]
 #define PK_DEQUEUE 4
 #endif
 
-template <int ROWS, bool MULTI>
+// MIXED (with MULTI; m2_build_mixed): the pairs' adapters differ in length -- m, k and what follows from them are the
+// lane's, read from its pair's matcher; thr[] is one array for the plan (one max_error_rate), ROWS holds the longest
+template <int ROWS, bool MULTI, bool MIXED = false>
 __global__ __launch_bounds__(256, CAH_DPP_WAVES(ROWS)) void k_dp_packed(DpArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t s_rowmask[];     // [128], or [n_adapters * CAH_MULTI_TAB_STRIDE]
     if (MULTI && a.queue_count && *a.queue_count == 0ull && (!a.queue_count_back || *a.queue_count_back == 0ull)) return;
@@ -1505,18 +1510,18 @@ __global__ __launch_bounds__(256, CAH_DPP_WAVES(ROWS)) void k_dp_packed(DpArgs a
     }
     __syncthreads();
 
-    const int m = mt->m, k = mt->k;
+    const int m0 = mt->m, k0 = mt->k;
     const int min_overlap = mt->min_overlap;
     const bool wildcard_ref = mt->wildcard_ref != 0;
     const int eff_full = mt->effective_length;
-    const int half_m = m / 2;
+    const int half_m0 = m0 / 2;
     // cost <= k  <=>  word < (k+1) << 20 (priority bits are clear in stored cells); costs never
     // exceed 64 here, so any k >= 200 behaves the same
 #ifdef CAH_DPP_PLAIN
-    const unsigned klim = (unsigned)(min(k, 200) + 1) << PK_COST_SHIFT;
+    const unsigned klim0 = (unsigned)(min(k0, 200) + 1) << PK_COST_SHIFT;
 #else
-    unsigned klim = (unsigned)(min(k, 200) + 1) << PK_COST_SHIFT;
-    asm volatile("" : "+v"(klim));                       // (a VGPR: as an SGPR operand it doubles the subtraction's issue time)
+    unsigned klim0 = (unsigned)(min(k0, 200) + 1) << PK_COST_SHIFT;
+    asm volatile("" : "+v"(klim0));                       // (a VGPR: as an SGPR operand it doubles the subtraction's issue time)
 #endif
 
     const int lane = wave_lane();
@@ -1559,6 +1564,13 @@ __global__ __launch_bounds__(256, CAH_DPP_WAVES(ROWS)) void k_dp_packed(DpArgs a
         auto table_index = [&](unsigned c) -> unsigned {
             return MULTI ? tab_base + multi_tab_index(c & 0xFFu) : (c & (CAH_TABLE_CHARS - 1));
         };
+        int m = m0, k = k0, half_m = half_m0;
+        unsigned klim = klim0;
+        if constexpr (MIXED) {
+            const CahMatcher* const ma = a.matcher + adapter;          // (adapter 0 for a lane without a pair)
+            m = ma->m; k = ma->k; half_m = m >> 1;
+            klim = (unsigned)(k + 1) << PK_COST_SHIFT;
+        }
         int64_t off = 0, n64 = 0;
         if (valid) read_extent(a.offsets, a.lens, a.uniform_first, a.uniform_len, r, off, n64);
         bool invalid = false;
@@ -1635,7 +1647,7 @@ __global__ __launch_bounds__(256, CAH_DPP_WAVES(ROWS)) void k_dp_packed(DpArgs a
 #endif
                 int nl = 0;                               // row 0 always has cost 0 <= k
                 unsigned cm_w = w_row0;                   // (m == 0: the candidate cell is row 0)
-                dp_rows_packed<1, ROWS>(w, (unsigned)mk, (unsigned)(mk >> 32), w_row0, nl, cm_w, last, m, klim,
+                dp_rows_packed<1, ROWS, MIXED>(w, (unsigned)mk, (unsigned)(mk >> 32), w_row0, nl, cm_w, last, m, klim,
                                         dpp_match_bit((unsigned)mk, 0), 1 <= last);
                 last_filled = last;                       // :484
                 if (last >= 1) lf_ran = last;
@@ -1679,7 +1691,7 @@ __global__ __launch_bounds__(256, CAH_DPP_WAVES(ROWS)) void k_dp_packed(DpArgs a
             stale_origin = lf_ran >= 1 ? j - pk_rel(stale_w) : 0;
         }
 #pragma unroll 1
-        for (int i = m; i >= 0; --i) {
+        for (int i = MIXED ? ROWS : m; i >= 0; --i) {      // (MIXED: last_filled <= the lane's m)
             const bool want = valid && do_scan && i <= last_filled;
             if (!__any(want)) continue;
             const unsigned wi = i == 0 ? w_row0 : get_row_packed<ROWS>(w, i);
@@ -1707,7 +1719,9 @@ __global__ __launch_bounds__(256, CAH_DPP_WAVES(ROWS)) void k_dp_packed(DpArgs a
             // reference's own tail k-mers of that adapter
             if (a.m2_hdr && merge && pair_tail) {
                 const int qs = max(b_origin, 0);
-                if (n - qs > (int)a.m2_hdr->lmax_row[b_refstop])
+                int lmax = (int)a.m2_hdr->lmax_row[b_refstop];
+                if constexpr (MIXED) lmax = min(lmax, m);              // (the adapter's own last class ends at its last row)
+                if (n - qs > lmax)
                     merge = m2_ref_present(a.m2_ref_list, a.m2_ref_begin[adapter], a.m2_ref_begin[adapter + 1], q, n, a.m2_hdr->ref_span);
             }
             if (merge)
@@ -2596,8 +2610,19 @@ hipError_t launch_uniform_check(const int64_t* offsets, int64_t n_reads, int64_t
 }
 
 hipError_t launch_dp(const DpArgs& a, int m, bool unit, bool back_adapter, int64_t max_items, int n_cus,
-                     hipStream_t s) {
+                     hipStream_t s, bool mixed) {
     const int grid = grid_for(max_items, 8, n_cus);
+    if (mixed) {
+        if (!(unit && back_adapter && a.pairs) || m > CAH_MAX_M) return hipErrorInvalidValue;
+        const size_t lds = sizeof(uint64_t) * (size_t)a.n_adapters * CAH_MULTI_TAB_STRIDE;
+        switch (dp_mixed_rows(m)) {
+            case 24: hipLaunchKernelGGL((k_dp_packed<24, true, true>), dim3(grid), dim3(256), lds, s, a); break;
+            case 32: hipLaunchKernelGGL((k_dp_packed<32, true, true>), dim3(grid), dim3(256), lds, s, a); break;
+            case 48: hipLaunchKernelGGL((k_dp_packed<48, true, true>), dim3(grid), dim3(256), lds, s, a); break;
+            default: hipLaunchKernelGGL((k_dp_packed<64, true, true>), dim3(grid), dim3(256), lds, s, a); break;
+        }
+        return hipGetLastError();
+    }
     if (unit && back_adapter) {
         // the common case: 3' adapter, unit costs -> one-word-per-cell kernel
 #define CAH_DPP_CASE(R)                                                                                            \

@@ -38,6 +38,12 @@
 // `wide` bitset): a whole-read pair that took the window of its one occurrence (CAH_M2_PAIR_PRECISE) falls back to the
 // full window then.
 //
+// Mixed lengths (m2_build_mixed): adapters that share a rate and a min_overlap agree row by row on thr_last, on lmax0 and on
+// every error class of the last column; they differ in where their rows end, in k and the k + 1 whole-adapter chunks.  The
+// classes, sub-classes and E0 groups are the longest adapter's, clipped per adapter; (i), (iii), (iv) hold per adapter
+// against its own sets; the prefilter kernel is the one-shape plans' (the header's m and k -- the longest's -- only group
+// the whole-read pairs into pages; every pair's window comes from its own matcher in k_multi_scan).
+//
 // Characters: A 0, C 1, G 2, T 3, either case; anything else 4 (no k-mer holds it, as in KmerFinder without wildcards:
 // _match_tables.py:81-98).  Two kinds of words, the newest character in the lowest bits:
 //   * what is LOOKED UP (bitmaps, directory, entries' keys, events) takes two bits per character, sixteen characters per
@@ -207,6 +213,9 @@ struct CahMulti2Header {
     // the corner the cell DP checks (see the head of this file): row i belongs to an error class that ends at lmax_row[i]
     int32_t ref_span;              // the widest tail window among the reference's k-mers
     uint8_t lmax_row[72];
+    // 1: the adapters differ in length (m2_build_mixed): m and k above are the LONGEST adapter's -- k_multi_stream groups
+    // the whole-read pairs by them, nothing else -- and k_multi_scan / the cell DP read every pair's own matcher
+    int32_t mixed;
 };
 
 // Is one of the reference's tail k-mers (list entries [begin, end): {code, q | window << 8}; whole-read k-mers are not in
@@ -269,22 +278,31 @@ inline std::vector<std::string> m2_chunks(const std::string& s, int chunks) {
     return out;
 }
 
-// Builds the tables for adapters of ONE shape (length m, thresholds thr_last[0..m] = threshold of row i in the last
-// column, kacc = thr of a last-row candidate, min_overlap).  ref[a]: the reference search sets of adapter a.
-// Returns false (t.hdr.ok = 0) when the plan does not fit: a k-mer longer than CAH_M2_MAXQ, too many entries,
-// non-monotone thresholds, an error-free class longer than a word, or search sets without the properties (i), (iii),
-// (iv) of this file's head.
-inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* thr_last, int kacc, int k, int min_overlap,
-                     const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t) {
+// The builder behind m2_build and m2_build_mixed.  thr_last[0..m]: threshold of row i in the last column, m the LONGEST
+// adapter's length; k_of[a]: thr of a last-row candidate of adapter a (= thr_last[its length]).  The error classes, their
+// sub-classes and the error-free groups are those of the longest adapter, CLIPPED per adapter to its own rows (a
+// sub-class that begins behind an adapter's last row adds no entry): the set of k-mer lengths -- the passes and mask
+// registers -- is what a plan of the longest length alone has.  Conditions (i), (iii), (iv) are checked per adapter
+// against that adapter's own reference sets, (iv) with windows that reach min(lmax_e, its length).
+inline bool m2_build_impl(const std::vector<std::string>& adapters, const int32_t* thr_last, const int* k_of, int min_overlap,
+                          const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t) {
     CahMulti2Header& h = t.hdr;
     h = CahMulti2Header();
     const int A = (int)adapters.size();
     if (A < 1 || A > 128) return false;
-    const int m = (int)adapters[0].size();
-    if (m < 1 || m > 64 || kacc < 0 || kacc != k) return false;
+    int m = 0, k = 0, m_min = 1 << 20;
+    for (int a = 0; a < A; a++) {
+        m = std::max(m, (int)adapters[(size_t)a].size());
+        m_min = std::min(m_min, (int)adapters[(size_t)a].size());
+        k = std::max(k, k_of[a]);
+    }
+    if (m_min < 1 || m > 64) return false;
     for (int i = std::max(min_overlap, 1) + 1; i <= m; i++)
         if (thr_last[i] < thr_last[i - 1] || thr_last[i] > thr_last[i - 1] + 1) return false;
-    if (min_overlap >= 1 && min_overlap <= m && thr_last[m] != kacc) return false;
+    for (int a = 0; a < A; a++) {
+        const int ma = (int)adapters[(size_t)a].size();
+        if (k_of[a] < 0 || (min_overlap >= 1 && min_overlap <= ma && thr_last[ma] != k_of[a])) return false;
+    }
     // error classes of the last column's rows
     struct Tail { int e, lmin, lmax; };
     std::vector<Tail> tails;
@@ -299,6 +317,7 @@ inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* th
     }
     if (lmax0 > CAH_M2_MAXQ) return false;
     h.n_adapters = A; h.m = m; h.k = k; h.min_overlap = min_overlap; h.lmax0 = lmax0;
+    h.mixed = m_min != m ? 1 : 0;
     h.rows_lo = lmax0;
     for (const Tail& tl : tails) if (tl.e == 1) h.rows_lo = tl.lmax;
     for (int i = 0; i < 72; i++) h.lmax_row[i] = 0;
@@ -335,7 +354,7 @@ inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* th
     h.ref_span = 0;
     for (int a = 0; a < A; a++) {
         const std::string& ad = adapters[(size_t)a];
-        if ((int)ad.size() != m) return false;
+        const int ma = (int)ad.size(), kacc = k_of[a];
         const std::vector<M2RefKmer>& rf = ref[(size_t)a];
         const size_t first = ents.size();
         auto add = [&](const std::string& s, int cls, int dlo, int dhi) -> bool {
@@ -357,24 +376,28 @@ inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* th
             return false;
         };
         // a last-row candidate (cost <= kacc) holds one of the k + 1 chunks of the whole adapter -- (i): a REF k-mer too
-        if (min_overlap <= m)
+        if (min_overlap <= ma)
             for (const std::string& s : m2_chunks(ad, kacc + 1)) {
                 if (!ref_has(s, CAH_M2_WHOLE)) return false;
                 if (!add(s, M2_W, 0, 255)) return false;
             }
         // (iv): the reference's own chunks of every error class, with windows that reach the class's last row
-        for (const Tail& tl : tails)
+        for (const Tail& tl : tails) {
+            if (tl.lmin > ma) continue;                                 // (a class of rows this adapter does not have)
             for (const std::string& s : m2_chunks(ad.substr(0, (size_t)tl.lmin), tl.e + 1))
-                if (!ref_has(s, tl.lmax)) return false;
+                if (!ref_has(s, std::min(tl.lmax, ma))) return false;
+        }
         for (const Sub& sb : subs) {
+            if (sb.la > ma) continue;
+            const int lb = std::min(sb.lb, ma);
             int o = 0;
             for (const std::string& s : m2_chunks(ad.substr(0, (size_t)sb.la), sb.e + 1)) {
-                if (!add(s, sb.e >= 2 ? M2_HI : M2_LO, sb.la - o - sb.e, sb.lb - o + sb.e)) return false;
+                if (!add(s, sb.e >= 2 ? M2_HI : M2_LO, sb.la - o - sb.e, lb - o + sb.e)) return false;
                 o += (int)s.size();
             }
         }
         // (iii): an exact overlap of i characters holds a prefix of the adapter that the reference looks for there
-        for (int i = row0; i <= lmax0; i++) {
+        for (int i = row0; i <= std::min(lmax0, ma); i++) {
             bool ok = false;
             for (const M2RefKmer& rk : rf)
                 if ((int)rk.kmer.size() <= i && ad.compare(0, rk.kmer.size(), rk.kmer) == 0 &&
@@ -382,7 +405,7 @@ inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* th
             if (!ok) return false;
         }
         for (const Sub& g : groups0)
-            if (!add(ad.substr(0, (size_t)g.la), M2_SHORT, g.la, g.lb)) return false;
+            if (g.la <= ma && !add(ad.substr(0, (size_t)g.la), M2_SHORT, g.la, std::min(g.lb, ma))) return false;
         // the reference's tail k-mers, for m2_ref_present
         for (const M2RefKmer& rk : rf) {
             if (rk.kmer.empty() || (int)rk.kmer.size() > CAH_M2_MAXQ) return false;
@@ -431,6 +454,7 @@ inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* th
         // error-free group as well has an entry of its own there: where its occurrence stands for rows of the last column
         // too, that entry's event finds the pair made and sets its "again" bit -- the pair then takes its full window)
         int pchunk = 0;
+        const int kacc = k_of[e.adapter];
         if (e.cls == M2_W && kacc + 1 <= 4) {
             const std::string& ad = adapters[(size_t)e.adapter];
             const std::vector<std::string> ch = m2_chunks(ad, kacc + 1);
@@ -498,10 +522,42 @@ inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* th
     t.prefix.assign((size_t)A, 0u);
     for (int a = 0; a < A; a++) {
         uint32_t p = 0;
-        for (int j = 0; j < 10; j++) p = (p << 3) | (j < m ? m2_code((unsigned char)adapters[(size_t)a][(size_t)j]) : 4u);
+        for (int j = 0; j < 10; j++) p = (p << 3) | (j < (int)adapters[(size_t)a].size() ? m2_code((unsigned char)adapters[(size_t)a][(size_t)j]) : 4u);
         t.prefix[(size_t)a] = p;
     }
     h.ok = 1;
+    return true;
+}
+
+// Builds the tables for adapters of ONE shape (length m, thresholds thr_last[0..m] = threshold of row i in the last
+// column, kacc = thr of a last-row candidate, min_overlap).  ref[a]: the reference search sets of adapter a.
+// Returns false (t.hdr.ok = 0) when the plan does not fit: a k-mer longer than CAH_M2_MAXQ, too many entries,
+// non-monotone thresholds, an error-free class longer than a word, or search sets without the properties (i), (iii),
+// (iv) of this file's head.
+inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* thr_last, int kacc, int k, int min_overlap,
+                     const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t) {
+    t.hdr = CahMulti2Header();
+    if (adapters.empty() || kacc < 0 || kacc != k) return false;
+    for (const std::string& ad : adapters) if (ad.size() != adapters[0].size()) return false;
+    const std::vector<int> k_of(adapters.size(), kacc);
+    return m2_build_impl(adapters, thr_last, k_of.data(), min_overlap, ref, t);
+}
+
+// The MIXED form: adapters of different lengths that share one min_overlap and agree on thr_last row by row (one
+// max_error_rate: thr_last[i] = floor(i * rate) whatever the length -- what the reference's file parser gives every
+// adapter of a file, parser.py:395-425).  thr_last: the LONGEST adapter's; k_of[a] = kacc of adapter a = thr_last[its
+// length].  Refused beyond m2_build's reasons: an adapter shorter than min_overlap (it never matches: no class W), or
+// shorter than the error-free rows (m2_exact_tail compares the plan's lmax0 <= 10 characters with every adapter's
+// prefix).  Rates below 1 / 11 are out for either builder: lmax0 would pass the ten characters of that compare, and the
+// chunks of the first error class the ten of a table key (CAH_M2_MAXQ).
+inline bool m2_build_mixed(const std::vector<std::string>& adapters, const int32_t* thr_last, const int* k_of, int min_overlap,
+                           const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t) {
+    t.hdr = CahMulti2Header();
+    if (min_overlap < 1) return false;
+    for (const std::string& ad : adapters) if ((int)ad.size() < min_overlap || ad.size() > 64) return false;
+    if (!m2_build_impl(adapters, thr_last, k_of, min_overlap, ref, t)) return false;
+    for (const std::string& ad : adapters)
+        if ((int)ad.size() < t.hdr.lmax0) { t.hdr.ok = 0; return false; }
     return true;
 }
 #endif

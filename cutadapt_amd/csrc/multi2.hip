@@ -809,6 +809,12 @@ __global__ __launch_bounds__(M2_WAVES * WAVE) void k_multi_stream(Multi2Args a) 
 #if !(defined(M2_ABL) && (M2_ABL & 1))
                     if (pos + 16 > tail_p0 && pos < n) {
                         const int kch = (pos - tail_base) >> 4;
+                        // (how many tail chunks there may be: the first one's words stay in registers, chunk kch >= 1 -- chunk
+                        // c >= 1 of this half-row, since the sweep begins inside it: multi2_read_len_ok's tail_base >= tail_off --
+                        // writes unit c - 1, whose characters are spent and whose own words, if it was a tail chunk, sit in
+                        // unit c - 2; the event pass below reads unit tail_unit0 + kch - 1 = the same.  Nothing here counts the
+                        // chunks: all M2_HALF of a half-row work.  multi2_read_len_ok grants five to mixed plans and keeps
+                        // one-shape plans at the four their batches have taken so far, so that no such plan changes its form.)
                         if (kch == 0) { tw0[0] = r2_prev; tw0[1] = r2_end; }
                         else {
                             uint32_t* const keep = reinterpret_cast<uint32_t*>(const_cast<unsigned char*>(row) + 16 * (c - 1));
@@ -997,7 +1003,13 @@ __global__ __launch_bounds__(M2_WAVES * WAVE) void k_multi_stream(Multi2Args a) 
 // go to k_dp_packed<ROWS, true>'s work list with a window that is safe for the cell DP (tail pairs: the full reach
 // m + k + 1, see multi2_model.cpp).
 // =============================================================================================
-template <int KIND>
+// MIXED (m2_build_mixed: adapters of different lengths): what a one-shape plan takes from matcher 0 once per block --
+// m, k, kacc (BackScanParams), the reach, the chunking of the whole adapter -- is the PAIR's, from a table of the plan's
+// lengths in LDS; the word form is the longest adapter's (KIND 1 when that has at most 32 characters, else KIND 0: a
+// shorter adapter sits top-aligned in the same word with its own pad rows; the explicit-row forms 2 and 3 have no pad
+// rows and stay one-shape) and so is thr_last (the adapters agree on every row they share).  The one-shape
+// instantiations are the code they were.
+template <int KIND, bool MIXED = false>
 __global__ __launch_bounds__(256, (KIND == 3 || KIND == 0) ? 4 : 5) void k_multi_scan(Multi2ScanArgs a) {
     constexpr int XR = KIND >= 2 ? KIND - 1 : 0;
     extern __shared__ __attribute__((aligned(16))) uint64_t s_scanmask[];   // [n_adapters * CAH_MULTI_TAB_STRIDE]
@@ -1011,21 +1023,41 @@ __global__ __launch_bounds__(256, (KIND == 3 || KIND == 0) ? 4 : 5) void k_multi
     __shared__ long long s_page;
     __shared__ unsigned long long s_gf, s_gb;
     const CahMatcher* mt = a.matcher;
+    uint32_t* s_mk = nullptr;                                           // MIXED: per adapter m | k << 8
+    if constexpr (MIXED) {
+        static_assert(KIND == 0 || KIND == 1, "the explicit-row forms are one-shape");
+        __shared__ uint32_t s_mk_store[128];
+        s_mk = s_mk_store;
+        mt = a.matcher + a.longest;
+    }
     if (*a.page_counter == 0ull) return;                                // (a round that found no tile left)
     // (pages are drawn from one counter: blocks beyond their number have nothing to do -- they leave before the tables are
     // copied, which is what a launch over a small batch would otherwise spend its time on)
     if ((unsigned long long)blockIdx.x >= *a.page_counter) return;
+    // (MIXED: mt is the LONGEST adapter, not adapter i's.  That is the entry of every adapter all the same: MIXED has KIND 0,
+    // which takes the 64-bit word as it is -- top-aligned by the adapter's own m when the plan was built --, or KIND 1, where
+    // every adapter has at most 32 characters and bs32_table_entry is that word's upper half whatever m <= 32 is passed)
     for (int i = threadIdx.x; i < a.n_adapters * CAH_MULTI_TAB_STRIDE; i += blockDim.x)
         s_scanmask[i] = KIND == 0 ? a.tab[i] : bs32_table_entry(a.tab[i], mt->m);
     for (int i = threadIdx.x; i <= CAH_MAX_M; i += blockDim.x) s_thr_last[i] = mt->thr_last[i];
     for (int i = threadIdx.x; i < 128; i += blockDim.x) {
         s_prefix[i] = i < a.n_adapters ? a.prefix[i] : 0u;
         s_xlat[i] = (uint8_t)m2_code((unsigned)i);
+        if constexpr (MIXED) s_mk[i] = i < a.n_adapters ? ((uint32_t)a.matcher[i].m | ((uint32_t)a.matcher[i].k << 8)) : 1u;
     }
     BackScanParams p;
     p.m = mt->m; p.k = mt->k; p.kacc = mt->kacc; p.min_overlap = mt->min_overlap; p.half_m = mt->m / 2;
-    const int reach = p.m + p.k + 1;
-    const int chunk_base = p.m / (p.k + 1), chunk_extra = p.m % (p.k + 1);
+    int reach = p.m + p.k + 1;
+    int chunk_base = p.m / (p.k + 1), chunk_extra = p.m % (p.k + 1);
+    // MIXED: the parameters of this lane's pair (kacc == k in a mixed plan: build_multi; behind the block's first barrier)
+    auto pair_params = [&](const unsigned adapter) {
+        if constexpr (MIXED) {
+            const uint32_t mk = s_mk[adapter & 127u];
+            p.m = (int)(mk & 255u); p.k = (int)(mk >> 8); p.kacc = p.k; p.half_m = p.m >> 1;
+            reach = p.m + p.k + 1;
+            chunk_base = p.m / (p.k + 1); chunk_extra = p.m - chunk_base * (p.k + 1);
+        }
+    };
     const int lane = wave_lane();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int n = a.uniform_len;
@@ -1082,6 +1114,7 @@ __global__ __launch_bounds__(256, (KIND == 3 || KIND == 0) ? 4 : 5) void k_multi
                     const unsigned flags = (unsigned)(pr >> 24) & 0xFFu, key = (unsigned)pr & 0xFFu;
                     const unsigned adapter = (unsigned)(pr >> 8) & 0xFFFFu;
                     const int64_t r = (int64_t)(pr >> 32);
+                    pair_params(adapter);
                     int j0w = max(0, ((int)key << CAH_KEY_SHIFT) - p.m - p.k - 1), jb = n;
                     unsigned precise = 0, tail0 = 0;
                     if (flags & CAH_M2_PAIR_PRECISE) {
@@ -1153,6 +1186,7 @@ __global__ __launch_bounds__(256, (KIND == 3 || KIND == 0) ? 4 : 5) void k_multi
                 key = (unsigned)pr & 0xFFu;
                 tab_base = adapter * CAH_MULTI_TAB_STRIDE;
             }
+            pair_params(adapter);
             int pad = 0;
             const uint8_t* q = frame_of(r, pad);
             // A tail page's pairs all have the same window (one class, one read length), from column 4 * key: the scan
@@ -1371,7 +1405,10 @@ bool multi2_read_len_ok(const CahMulti2Header& h, int n) {
     int p0 = n;
     for (int j = 0; j < h.tq_n; j++) p0 = std::min(p0, std::max(0, n + h.tq_qc[j] - 1 - h.tq_open[j]));
     const int tail_base = p0 & ~15;
-    if (tail_base < tail_off || n - tail_base > 64) return false;
+    // (a mixed plan may use the whole last half-row, five chunks: the words of tail chunk c >= 1 wait in row unit c - 1 of that
+    // half-row whatever their number, the first chunk's in registers -- what a 64-mer among shorter adapters needs at 150
+    // characters.  One-shape plans keep the four chunks they were measured with.)
+    if (tail_base < tail_off || n - tail_base > (h.mixed ? M2_ROW : 64)) return false;
     return true;
 }
 
@@ -1417,6 +1454,13 @@ hipError_t launch_multi_scan(const Multi2ScanArgs& a, int64_t max_pages, int n_c
     const int64_t cap = (int64_t)8 * n_cus;
     const dim3 grid((unsigned)(need < cap ? need : cap));
     const size_t lds = sizeof(uint64_t) * (size_t)a.n_adapters * CAH_MULTI_TAB_STRIDE;
+    if (a.mixed) {
+        // (the launcher's caller maps the explicit-row kinds to the 64-bit form: api.cpp)
+        if (a.kind == 1) hipLaunchKernelGGL((k_multi_scan<1, true>), grid, dim3(256), lds, s, a);
+        else if (a.kind == 0) hipLaunchKernelGGL((k_multi_scan<0, true>), grid, dim3(256), lds, s, a);
+        else return hipErrorInvalidValue;
+        return hipGetLastError();
+    }
     switch (a.kind) {
         case 1: hipLaunchKernelGGL((k_multi_scan<1>), grid, dim3(256), lds, s, a); break;
         case 2: hipLaunchKernelGGL((k_multi_scan<2>), grid, dim3(256), lds, s, a); break;

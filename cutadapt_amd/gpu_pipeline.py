@@ -175,6 +175,7 @@ class _Worker:
         self._ws = None
         self.n = self.n_bytes = 0
         self.busy_s, self.chunks, self.bytes_in, self.reads_in = 0.0, 0, 0, 0   # per-device rates (trim_fastq_gpu's "per_device")
+        self._mixed, self.stream_chunks = None, 0              # _mixed_plan's answer for self.plan; calls that streamed
         self.stream.wait_stream(torch.cuda.current_stream(self.device))   # (the zeroing / uploads above ran on it)
 
     def _ensure(self, nbytes: int):
@@ -327,6 +328,28 @@ class _Worker:
             self.modify(n, o.get("pre"), o.get("post"), limits)
         return self.finish(data, n, n_bytes)
 
+    def _mixed_plan(self) -> bool:
+        """is self.plan a plan of several adapters whose only multi-adapter form is the streaming one (mixed lengths)?
+        Such a plan answers "stream" for some read length and "sequential" -- not "fused" -- where it does not stream."""
+        m = self._mixed
+        if m is None:
+            p = self.plan
+            m = bool(hasattr(_lib.lib(), "cah_match_batch_frames") and getattr(p, "n_adapters", 0) >= 2 and
+                     p.multi_kind(1000) == "sequential" and any(p.multi_kind(k) == "stream" for k in range(16, 161, 8)))
+            self._mixed = m
+            self._frames = {}
+        return m
+
+    def _stream_frame(self, longest: int) -> int:
+        """the frame length for a chunk whose longest view has ``longest`` characters: the shortest length from there up to
+        160 that the plan streams at (0: none -- the plain entry point)"""
+        longest = max(int(longest), 16)
+        f = self._frames.get(longest)
+        if f is None:
+            f = next((k for k in range(longest, 161) if self.plan.multi_kind(k) == "stream"), 0)
+            self._frames[longest] = f
+        return f
+
     def modify(self, n: int, pre, post, limits=None):
         """The read-modifying steps of a loaded chunk on this worker's stream (reference cli.py:938-973): ``pre`` (-u,
         --nextseq-trim, -q) -> adapter step (``self.plan``; None: no adapters) -> ``post`` (--poly-a, -l) and the
@@ -458,23 +481,38 @@ class _Worker:
                 self._ws = torch.empty(ws_need + ws_need // 4, dtype=torch.uint8, device=self.device)
             reversed_reads = bool(self.opts.get("reversed"))
 
+            # A plan of several adapters of DIFFERENT lengths (the mixed form, csrc/api.cpp: build_multi_mixed) has no fused
+            # kernels behind its streaming form: through the plain entry point its ragged views would go adapter by adapter.
+            # Such a plan takes the chunk's views in end-aligned frames (cah_match_batch_frames) of the shortest length from
+            # the chunk's longest view up that the plan streams at -- one look at that maximum per chunk, on this stream.
+            # Every other plan keeps the plain entry point.
+            frame = 0
+            if self._mixed_plan():
+                frame = self._stream_frame(int(wlen.max().item()))
+
+            def call_match(seqs, off, ln, res):
+                args = (res.out6.data_ptr(), res.best_adapter.data_ptr(), res.status.data_ptr(), self._ws.data_ptr(),
+                        self._ws.numel(), sp)
+                if frame:
+                    _lib.check(L.cah_match_batch_frames(self.plan.handle, seqs.data_ptr(), off.data_ptr(), ln.data_ptr(), frame,
+                                                        n, *args))
+                    self.stream_chunks += _lib.last_multi_path() == "stream"
+                else:
+                    _lib.check(L.cah_match_batch(self.plan.handle, seqs.data_ptr(), off.data_ptr(), ln.data_ptr(), n, *args))
+
             def match_views(off, ln):
                 """the plan on the views (off, ln) of the chunk -> self.res.  Rightmost* adapters (reference adapters.py:766,
                 :870: the reversed adapter on the reversed read): the views reversed into a second buffer at the same offsets
                 (cah_reverse_reads_batch), matched there, the read coordinates mirrored back (:777-785)"""
                 if not reversed_reads:
-                    _lib.check(L.cah_match_batch(self.plan.handle, self.d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n,
-                                                 self.res.out6.data_ptr(), self.res.best_adapter.data_ptr(),
-                                                 self.res.status.data_ptr(), self._ws.data_ptr(), self._ws.numel(), sp))
+                    call_match(self.d_in, off, ln, self.res)
                     keepalive.append(ln)
                     return
                 if getattr(self, "d_rc", None) is None or self.d_rc.numel() < self.d_in.numel():
                     self.d_rc = torch.empty(self.d_in.numel(), dtype=torch.uint8, device=self.device)
                 _lib.check(L.cah_reverse_reads_batch(self.d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, off.data_ptr(),
                                                      self.d_rc.data_ptr(), sp))
-                _lib.check(L.cah_match_batch(self.plan.handle, self.d_rc.data_ptr(), off.data_ptr(), ln.data_ptr(), n,
-                                             self.res.out6.data_ptr(), self.res.best_adapter.data_ptr(),
-                                             self.res.status.data_ptr(), self._ws.data_ptr(), self._ws.numel(), sp))
+                call_match(self.d_rc, off, ln, self.res)
                 o6 = self.res.out6[:n]
                 q0, q1 = ln - o6[:, 3], ln - o6[:, 2]
                 o6[:, 2].copy_(q0)
@@ -499,9 +537,7 @@ class _Worker:
                 _lib.check(L.cah_revcomp_reads_batch(self.d_in.data_ptr(), voff.data_ptr(), wl.data_ptr(), n, voff.data_ptr(),
                                                      self.d_rc.data_ptr(), 1, None, sp))
                 r2 = self.res_rc
-                _lib.check(L.cah_match_batch(self.plan.handle, self.d_rc.data_ptr(), voff.data_ptr(), wl.data_ptr(), n,
-                                             r2.out6.data_ptr(), r2.best_adapter.data_ptr(), r2.status.data_ptr(),
-                                             self._ws.data_ptr(), self._ws.numel(), sp))
+                call_match(self.d_rc, voff, wl, r2)
                 fwd, rev = self.res.status[:n] == 1, r2.status[:n] == 1
                 zero = torch.zeros((), dtype=torch.int32, device=self.device)
                 use = torch.where(rev, r2.out6[:n, 4], zero) > torch.where(fwd, self.res.out6[:n, 4], zero)
@@ -879,6 +915,7 @@ def _take_worker(plan, kinds, dev, opts) -> "_Worker":
         w.rc_count.zero_()
     w._ws = None
     w.busy_s, w.chunks, w.bytes_in, w.reads_in = 0.0, 0, 0, 0
+    w._mixed, w.stream_chunks = None, 0                         # (what _mixed_plan found out about the worker's last plan)
     return w
 
 
@@ -1113,7 +1150,9 @@ def _per_device(feeders, wall: float) -> Dict[str, dict]:
                               "reads_in": int(sum(getattr(w, "reads_in", 0) for w in ws)),
                               "GB_per_s_in": nbytes / wall / 1e9 if wall > 0 else 0.0,
                               "busy_fraction": (sum(w.busy_s for w in ws) / (wall * len(ws))) if ws and wall > 0 else 0.0,
-                              "cpus": len(f.cpus) if f.cpus else None}
+                              "cpus": len(f.cpus) if f.cpus else None,
+                              # matching calls of a mixed-length plan that took the streaming multi-adapter form
+                              "stream_calls": int(sum(w.stream_chunks for w in ws))}
     return out
 
 

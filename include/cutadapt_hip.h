@@ -139,7 +139,13 @@ int cah_plan_n_kmer_entries(const cah_plan *plan, int32_t adapter, int32_t *out)
 int cah_plan_prefilter_kind(const cah_plan *plan, int32_t adapter, int32_t *out);
 /* how a batch of equally long reads of `read_len` characters is matched against ALL adapters of the plan
  * (MultipleAdapters.match_to, adapters.py:1265-1286): one adapter after the other, one fused prefilter pass over
- * (read, adapter) pairs, or its streaming form (k_multi_stream: LDS-staged reads, pairs in pages by window class) */
+ * (read, adapter) pairs, or its streaming form (k_multi_stream: LDS-staged reads, pairs in pages by window class).
+ * Adapters of DIFFERENT lengths (the mixed form): 8..128 plain-ACGT 3' adapters, all scan-eligible, one min_overlap and
+ * one max_error_rate (thresholds that agree row by row -- a plan from absolute max_errors does not), answer STREAM for
+ * the read lengths the streaming kernels take (16..160, less where the longest adapter's tail windows reach further back
+ * than the last half-row of the read that the prefilter keeps in LDS) and SEQUENTIAL otherwise: there is no fused form behind the mixed one.  It needs
+ * 8 adapters whatever CAH_MULTI_MIN says (CAH_MULTI_MIXED_MIN >= 2 lowers that for experiments); CAH_NO_MULTI_MIXED=1
+ * turns it off (so do CAH_NO_MULTI and CAH_NO_MULTI2): such a plan then takes the per-adapter loop. */
 #define CAH_MULTI_SEQUENTIAL 0
 #define CAH_MULTI_FUSED 1
 #define CAH_MULTI_STREAM 2
