@@ -451,8 +451,12 @@ __global__ __launch_bounds__(256) void k_index_lookup(IndexArgs a) {
         if (m > best_m || (m == best_m && e < best_e)) { best_ad = ad; best_e = e; best_m = m; best_len = L; }
     }
     int32_t* o = a.out6 + r * 6;
-    if (non_ascii) { a.status[r] = CAH_INVALID; if (a.best_adapter) a.best_adapter[r] = -1; return; }
-    if (best_ad < 0) { a.status[r] = CAH_NONE; if (a.best_adapter) a.best_adapter[r] = -1; return; }
+    if (non_ascii || best_ad < 0) {                      // six zeros, as cah_match_batch leaves a row without a match
+        for (int k = 0; k < 6; k++) o[k] = 0;
+        a.status[r] = non_ascii ? CAH_INVALID : CAH_NONE;
+        if (a.best_adapter) a.best_adapter[r] = -1;
+        return;
+    }
     // _make_prefix_match / _make_suffix_match (:1345-1371): the INDEXED length is reported, even for
     // a shorter read
     o[0] = 0;
@@ -547,8 +551,12 @@ __global__ __launch_bounds__(256) void k_index_lookup_wide(IndexArgs a) {
     // the indexed lengths beyond the read's own: all look the whole read up, the longest reports
     if (li >= 0) probe(n, a.lengths[0]);
     int32_t* o = a.out6 + r * 6;
-    if (non_ascii) { a.status[r] = CAH_INVALID; if (a.best_adapter) a.best_adapter[r] = -1; return; }
-    if (best_ad < 0) { a.status[r] = CAH_NONE; if (a.best_adapter) a.best_adapter[r] = -1; return; }
+    if (non_ascii || best_ad < 0) {                      // six zeros, as cah_match_batch leaves a row without a match
+        for (int k = 0; k < 6; k++) o[k] = 0;
+        a.status[r] = non_ascii ? CAH_INVALID : CAH_NONE;
+        if (a.best_adapter) a.best_adapter[r] = -1;
+        return;
+    }
     o[0] = 0;
     o[1] = a.adapters[best_ad].m;
     o[2] = prefix ? 0 : n - best_len;
@@ -820,10 +828,11 @@ int cah_index_lookup_batch(const cah_index* ix, const uint8_t* d_seqs, const int
                            const int32_t* d_lens, int64_t n_reads, int32_t* d_out6, int32_t* d_best_adapter,
                            uint8_t* d_status, void* stream) {
     if (!ix) return cah_set_error_(CAH_EINVAL, "cah_index_lookup_batch: index is NULL");
-    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "n_reads < 0");
+    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "cah_index_lookup_batch: n_reads < 0");
     if (n_reads == 0) return CAH_OK;
     if (!d_offsets || !d_out6 || !d_status) return cah_set_error_(CAH_EINVAL, "cah_index_lookup_batch: NULL argument");
     if (ix->lengths.empty()) {                         // nothing indexed: the reference's loop over lengths finds nothing (:1502)
+        IDX_TRY(hipMemsetAsync(d_out6, 0, sizeof(int32_t) * 6 * (size_t)n_reads, (hipStream_t)stream));
         IDX_TRY(hipMemsetAsync(d_status, CAH_NONE, (size_t)n_reads, (hipStream_t)stream));
         if (d_best_adapter) IDX_TRY(hipMemsetAsync(d_best_adapter, 0xFF, sizeof(int32_t) * (size_t)n_reads, (hipStream_t)stream));
         return CAH_OK;
@@ -847,7 +856,7 @@ int cah_index_lookup_batch(const cah_index* ix, const uint8_t* d_seqs, const int
 int cah_index_lookup_batch_host(const cah_index* ix, const uint8_t* seqs, const int64_t* offsets, int64_t n_reads,
                                 int32_t* out6, int32_t* best_adapter, uint8_t* status) {
     if (!ix) return cah_set_error_(CAH_EINVAL, "cah_index_lookup_batch_host: index is NULL");
-    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "n_reads < 0");
+    if (n_reads < 0) return cah_set_error_(CAH_EINVAL, "cah_index_lookup_batch_host: n_reads < 0");
     if (n_reads == 0) return CAH_OK;
     if (!offsets || !out6 || !status) return cah_set_error_(CAH_EINVAL, "cah_index_lookup_batch_host: NULL argument");
     const int64_t total = offsets[n_reads];

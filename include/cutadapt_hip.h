@@ -562,6 +562,19 @@ int cah_index_info(const cah_index *index, int64_t *n_strings, int32_t *n_ambigu
 /* host-side dictionary query of one string (introspection / tests) */
 int cah_index_get(const cah_index *index, const char *s, int32_t len, int32_t *found,
                   int32_t *adapter, int32_t *errors, int32_t *matches);
+/* One lookup per read; all pointers are device pointers, asynchronous on `stream`.
+ *   d_lens == NULL: read r is d_seqs[d_offsets[r] .. d_offsets[r + 1]) and d_offsets holds n_reads + 1 entries;
+ *   d_lens != NULL: read r is the window d_seqs[d_offsets[r] .. d_offsets[r] + d_lens[r]) of a parent buffer and
+ *                   d_offsets holds n_reads entries.  d_lens[r] >= 0 is the caller's duty; a length above
+ *                   CAH_MAX_READ_LEN gives CAH_INVALID and none of the read's bytes are touched.
+ * Only the affix of the longest indexed length is read (from the anchored end), nothing outside the read / window.
+ * Every row r < n_reads is written, no other row:
+ *   CAH_MATCH    out6 as above, best_adapter = the adapter's index;
+ *   CAH_NONE     out6 = six zeros (as cah_match_batch leaves it), best_adapter = -1;
+ *   CAH_INVALID  a byte >= 0x80 WITHIN the longest indexed affix (bytes the lookup does not read are not reported;
+ *                cah_validate_ascii_batch checks whole reads): out6 = six zeros, best_adapter = -1.
+ * d_best_adapter may be NULL.  n_reads == 0 returns CAH_OK and writes nothing; n_reads < 0 or a NULL index, d_offsets,
+ * d_out6 or d_status is CAH_EINVAL (the message names cah_index_lookup_batch) and nothing is launched. */
 int cah_index_lookup_batch(const cah_index *index, const uint8_t *d_seqs, const int64_t *d_offsets,
                            const int32_t *d_lens, int64_t n_reads, int32_t *d_out6,
                            int32_t *d_best_adapter, uint8_t *d_status, void *stream);
