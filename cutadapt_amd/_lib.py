@@ -25,7 +25,7 @@ PROF_FILTER, PROF_DP, PROF_COMPARER, PROF_SCAN, PROF_MERGE, PROF_N = 0, 1, 2, 3,
 EXPORTED_SYMBOLS = [
     "cah_abi_version", "cah_build_id", "cah_last_error", "cah_device_count", "cah_set_device", "cah_device_info",
     "cah_plan_create", "cah_plan_destroy", "cah_plan_n_adapters", "cah_plan_effective_length",
-    "cah_plan_n_kmer_entries", "cah_plan_prefilter_kind", "cah_plan_multi_kind", "cah_last_multi_path", "cah_plan_debug_matcher", "cah_plan_debug_lean", "cah_locate_batch", "cah_kmers_present_batch", "cah_match_batch", "cah_match_batch_uniform", "cah_match_batch_suffix_views", "cah_match_batch_views", "cah_match_batch_frames", "cah_set_deferred_errors", "cah_linked_views", "cah_linked_match_batch_uniform",
+    "cah_plan_n_kmer_entries", "cah_plan_prefilter_kind", "cah_plan_multi_kind", "cah_plan_multi_groups", "cah_last_multi_path", "cah_plan_debug_matcher", "cah_plan_debug_lean", "cah_locate_batch", "cah_kmers_present_batch", "cah_match_batch", "cah_match_batch_uniform", "cah_match_batch_suffix_views", "cah_match_batch_views", "cah_match_batch_frames", "cah_set_deferred_errors", "cah_linked_views", "cah_linked_match_batch_uniform",
     "cah_workspace_bytes", "cah_plan_workspace_bytes", "cah_validate_ascii_batch", "cah_reverse_reads_batch", "cah_revcomp_reads_batch", "cah_locate_batch_host",
     "cah_kmers_present_batch_host", "cah_match_batch_host", "cah_locate_debug_host", "cah_match_one_host", "cah_locate_one_host", "cah_profile_enable",
     "cah_profile_reset", "cah_profile_read", "cah_synth_reads",
@@ -114,6 +114,8 @@ def lib():
     L.cah_plan_n_kmer_entries.argtypes = [vp, i32, C.POINTER(i32)]
     L.cah_plan_prefilter_kind.argtypes = [vp, i32, C.POINTER(i32)]
     L.cah_plan_multi_kind.argtypes = [vp, i32, C.POINTER(i32)]
+    if hasattr(L, "cah_plan_multi_groups") or not any_abi:
+        L.cah_plan_multi_groups.argtypes = [vp, C.POINTER(i32)]
     L.cah_plan_debug_matcher.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cah_plan_debug_lean.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cah_locate_batch.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp, vp, C.c_size_t, vp]
@@ -369,6 +371,13 @@ class Plan:
         out = C.c_int32(0)
         check(lib().cah_plan_multi_kind(self._h, read_len, C.byref(out)))
         return ("sequential", "fused", "stream")[out.value]
+
+    def multi_groups(self) -> int:
+        """table sets of the streaming multi-adapter form a batch goes through: 0 -- the plan has none --, 1, or the number
+        of GROUPS of a plan of more adapters (129..1024) or more k-mers than one table holds"""
+        out = C.c_int32(0)
+        check(lib().cah_plan_multi_groups(self._h, C.byref(out)))
+        return out.value
 
     def n_kmer_entries(self, adapter: int = 0) -> int:
         out = C.c_int32(0)

@@ -166,6 +166,17 @@ struct LongDeviceCopy {
     int32_t* d_ncnt = nullptr;
 };
 
+// one table set of the streaming multi-adapter form on a device (multi2.h: M2Tables)
+struct M2DeviceTables {
+    CahMulti2Header* d_m2hdr = nullptr;
+    uint16_t* d_m2dir = nullptr;
+    CahM2Slot* d_m2entries = nullptr;
+    uint32_t* d_m2bitmap = nullptr;
+    uint32_t* d_m2prefix = nullptr;
+    int32_t* d_m2refbegin = nullptr;
+    uint32_t* d_m2reflist = nullptr;
+};
+
 struct PlanDeviceCopy {
     bool ready = false;
     int n_cus = 256;
@@ -179,14 +190,8 @@ struct PlanDeviceCopy {
     uint32_t* d_mbitmap = nullptr;
     uint64_t* d_mscan = nullptr;          // [n_adapters][CAH_MULTI_TAB_STRIDE] padded match words (cost scan)
     uint64_t* d_mrow = nullptr;           // ... row bitsets (cell DP)
-    // ... its streaming form (multi2.h; m2.hdr.ok only)
-    CahMulti2Header* d_m2hdr = nullptr;
-    uint16_t* d_m2dir = nullptr;
-    CahM2Slot* d_m2entries = nullptr;
-    uint32_t* d_m2bitmap = nullptr;
-    uint32_t* d_m2prefix = nullptr;
-    int32_t* d_m2refbegin = nullptr;
-    uint32_t* d_m2reflist = nullptr;
+    // ... its streaming form (multi2.h): the tables of every group -- one (m2.hdr.ok) or, for a grouped plan, MultiPlan::groups'
+    std::vector<M2DeviceTables> d_m2;
     std::vector<LongDeviceCopy> d_long;   // one per matcher (null pointers for bare k-mer finders)
     // the one-read kernel's table images ([0]: Aligner.locate, no prefilter; [1]: match_to), built by its first call
     void* d_tiny_image[2] = {nullptr, nullptr};
@@ -205,7 +210,24 @@ struct MultiPlan {
     // take goes through the per-adapter loop
     bool mixed = false;
     int longest = 0;                      // the (first) longest adapter: word form, ROWS and thr_last come from it
+    // GROUPS of tables (build_multi_groups; multi2.h: m2_build_groups): a plan of more adapters than one table holds.
+    // hdr.ok and m2.hdr.ok stay 0, `mixed` is set -- like a mixed plan it has no fused form behind it --, every group has
+    // tables of its own over the adapters [base, base + count); scan_tab / row_tab are the plan's, indexed from base
+    struct Group { int base = 0, count = 0, longest = 0; M2Tables m2; };   // longest: the group's, as an index INSIDE it
+    std::vector<Group> groups;
+    bool groups_one_length = false;       // a grouped plan whose adapters are all equally long (CAH_NO_MULTI_MIXED does not mean it)
     MultiPlan() { memset(&hdr, 0, sizeof(hdr)); memset(&m2.hdr, 0, sizeof(m2.hdr)); }
+    // the table sets a batch goes through, in order: the groups', or the one of a plan that fits a table (none: no streaming form)
+    int n_tables() const { return !groups.empty() ? (int)groups.size() : (m2.hdr.ok ? 1 : 0); }
+    const M2Tables& tables(int g) const { return groups.empty() ? m2 : groups[(size_t)g].m2; }
+    int group_base(int g) const { return groups.empty() ? 0 : groups[(size_t)g].base; }
+    int group_count(int g, int n_plan) const { return groups.empty() ? n_plan : groups[(size_t)g].count; }
+    int group_longest(int g) const { return groups.empty() ? (mixed ? longest : 0) : groups[(size_t)g].longest; }
+    int largest_group(int n_plan) const {
+        int c = groups.empty() ? n_plan : 0;
+        for (const Group& g : groups) c = std::max(c, g.count);
+        return c;
+    }
 };
 
 // Host tables are built (and validated) at creation; the HBM copy for a device is made the
@@ -271,15 +293,18 @@ static int plan_on_device(const cah_plan* plan, const PlanDeviceCopy** out) {
             }
             CAH_UPLOAD(dc.d_mscan, mp.scan_tab)
             CAH_UPLOAD(dc.d_mrow, mp.row_tab)
-            if (mp.m2.hdr.ok) {
-                HIP_TRY(hipMalloc((void**)&dc.d_m2hdr, sizeof(CahMulti2Header)));
-                HIP_TRY(hipMemcpy(dc.d_m2hdr, &mp.m2.hdr, sizeof(CahMulti2Header), hipMemcpyHostToDevice));
-                CAH_UPLOAD(dc.d_m2dir, mp.m2.dir)
-                CAH_UPLOAD(dc.d_m2entries, mp.m2.entries)
-                CAH_UPLOAD(dc.d_m2bitmap, mp.m2.bitmap)
-                CAH_UPLOAD(dc.d_m2prefix, mp.m2.prefix)
-                CAH_UPLOAD(dc.d_m2refbegin, mp.m2.ref_begin)
-                CAH_UPLOAD(dc.d_m2reflist, mp.m2.ref_list)
+            dc.d_m2.assign((size_t)mp.n_tables(), M2DeviceTables());
+            for (int g = 0; g < mp.n_tables(); g++) {
+                const M2Tables& t = mp.tables(g);
+                M2DeviceTables& dt = dc.d_m2[(size_t)g];
+                HIP_TRY(hipMalloc((void**)&dt.d_m2hdr, sizeof(CahMulti2Header)));
+                HIP_TRY(hipMemcpy(dt.d_m2hdr, &t.hdr, sizeof(CahMulti2Header), hipMemcpyHostToDevice));
+                CAH_UPLOAD(dt.d_m2dir, t.dir)
+                CAH_UPLOAD(dt.d_m2entries, t.entries)
+                CAH_UPLOAD(dt.d_m2bitmap, t.bitmap)
+                CAH_UPLOAD(dt.d_m2prefix, t.prefix)
+                CAH_UPLOAD(dt.d_m2refbegin, t.ref_begin)
+                CAH_UPLOAD(dt.d_m2reflist, t.ref_list)
             }
 #undef CAH_UPLOAD
         }
@@ -729,8 +754,69 @@ static void m2_ref_sets(const cah_adapter_desc* descs, int n, std::vector<std::s
     }
 }
 
-// The MIXED form of the streaming multi-adapter path: 8..128 plain-ACGT 3' adapters of DIFFERENT lengths that are all
-// scan-eligible with kacc == k, share one min_overlap and agree on thr[] and, row by row, on thr_last[] -- one
+// What the mixed form and the groups of tables ask of a WHOLE plan: plain-ACGT 3' adapters that are all scan-eligible
+// with kacc == k, share one min_overlap and agree on thr[] and, row by row, on thr_last[]; search sets that are whole-read
+// or tail sets.  longest: the (first) longest adapter; k_of[a] = kacc of adapter a.
+static bool multi_stream_eligible(const cah_adapter_desc* descs, int n, const cah_plan* plan, int& longest, std::vector<int>& k_of) {
+    longest = 0;
+    for (int a = 1; a < n; a++) if (plan->matchers[(size_t)a].m > plan->matchers[(size_t)longest].m) longest = a;
+    const CahMatcher& ml = plan->matchers[(size_t)longest];
+    k_of.assign((size_t)n, 0);
+    for (int a = 0; a < n; a++) {
+        const cah_adapter_desc& d = descs[a];
+        const CahMatcher& mt = plan->matchers[(size_t)a];
+        if (d.kind != CAH_KIND_ALIGNER || !mt.scan_ok || d.wildcard_ref || d.wildcard_query) return false;
+        if (mt.m < 1 || mt.m > CAH_MAX_M || mt.kacc != mt.k || mt.min_overlap != ml.min_overlap) return false;
+        if (memcmp(mt.thr, ml.thr, sizeof(mt.thr)) != 0) return false;
+        for (int i = 0; i <= mt.m; i++) if (mt.thr_last[i] != ml.thr_last[i]) return false;
+        for (int i = 0; i < mt.m; i++) { const char c = d.sequence[i]; if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return false; }
+        if (d.n_kmer_sets <= 0 || !d.kmer_sets || d.kmer_ref_wildcards || d.kmer_query_wildcards) return false;
+        for (int si = 0; si < d.n_kmer_sets; si++) {
+            const cah_kmer_set& ks = d.kmer_sets[si];
+            if (!((ks.start == 0 && ks.stop == 0) || (ks.start < 0 && ks.stop == 0 && ks.start >= -255))) return false;
+            for (int t = 0; t < ks.n_kmers; t++) if (!ks.kmers[t] || !*ks.kmers[t]) return false;
+        }
+        k_of[(size_t)a] = mt.kacc;
+    }
+    return true;
+}
+
+// GROUPS of tables (multi2.h: m2_build_groups): an eligible plan of 129..CAH_MULTI_MAX_PLAN_ADAPTERS (1 024) adapters, of
+// one length or mixed, and a mixed plan of up to 128 adapters whose one table is refused for CAPACITY (more than
+// CAH_M2_MAX_ENTRIES k-mers: 96 adapters at rate 0.2).  The batch goes through every group's prefilter, scan and cell DP
+// against the same best keys -- G passes over the batch where the per-adapter loop makes n.  Like a mixed plan it has
+// no fused form behind it: what the streaming kernels do not take (reads over 160 characters, a ragged packed batch
+// without frames) is the loop's.  CAH_NO_MULTI_GROUPS=1 (asked at every call) sends such a plan to the loop (A/B, parity).
+// Measured against the loop: profiles/multi_groups/ab.json (profiles/scripts/multi_groups_ab.py).
+static void build_multi_groups(cah_plan* plan, int n, int longest, const std::vector<int>& k_of,
+                               const std::vector<std::string>& ads, const std::vector<std::vector<M2RefKmer>>& ref) {
+    MultiPlan& mp = plan->multi;
+    const CahMatcher& ml = plan->matchers[(size_t)longest];
+    std::vector<M2Group> gs;
+    // (a group of 128 adapters with a nearly full table passes the 160 KB of LDS k_multi_stream can have -- multi2_read_len_ok
+    // would send every batch of the plan to the loop for that one group: it is halved instead)
+    auto fits = [](const M2Tables& t) { return multi2_lds_bytes(t.hdr) <= 160 * 1024; };
+    if (!m2_build_groups(ads, ml.thr_last, k_of.data(), ml.min_overlap, ref, gs, nullptr, fits) || gs.size() < 2) return;
+    mp.groups.resize(gs.size());
+    for (size_t g = 0; g < gs.size(); g++) {
+        MultiPlan::Group& dst = mp.groups[g];
+        dst.base = gs[g].base; dst.count = gs[g].count;
+        dst.m2 = std::move(gs[g].t);
+        dst.longest = 0;
+        for (int a = 1; a < dst.count; a++)
+            if (plan->matchers[(size_t)(dst.base + a)].m > plan->matchers[(size_t)(dst.base + dst.longest)].m) dst.longest = a;
+    }
+    memset(&mp.m2.hdr, 0, sizeof(mp.m2.hdr));
+    fill_multi_tabs(plan, n, mp);
+    mp.mixed = true;                                          // (routing: no fused form behind the groups)
+    mp.longest = longest;
+    mp.groups_one_length = true;
+    for (int a = 1; a < n; a++) mp.groups_one_length = mp.groups_one_length && plan->matchers[(size_t)a].m == plan->matchers[0].m;
+}
+
+// The MIXED form of the streaming multi-adapter path: 8..128 plain-ACGT 3' adapters of DIFFERENT lengths in ONE table
+// (more adapters, or more k-mers than the table holds: groups of tables, build_multi_groups -- up to 1 024 adapters) that
+// are all scan-eligible with kacc == k, share one min_overlap and agree on thr[] and, row by row, on thr_last[] -- one
 // max_error_rate: what `-a file:` gives the adapters of a real FASTA (TruSeq 33 / 34, Nextera 19, small RNA 21 ...).
 // A plan built from absolute max_errors has another rate per length and stays on the per-adapter loop.  There is no
 // older fused form behind it (multi.hip is one-shape): batches the streaming form does not take (reads over 160
@@ -742,37 +828,26 @@ static void build_multi_mixed(const cah_adapter_desc* descs, int n, cah_plan* pl
     if (env_flag_early("CAH_NO_MULTI_MIXED") || env_flag_early("CAH_NO_MULTI2")) return;
     int min_adapters = 8;
     if (const char* e = getenv("CAH_MULTI_MIXED_MIN")) { const int v = atoi(e); if (v >= 2) min_adapters = v; }
-    if (n < min_adapters || n > CAH_MULTI_MAX_ADAPTERS || n > 128) return;
+    if (n < min_adapters || n > CAH_MULTI_MAX_PLAN_ADAPTERS) return;
     int longest = 0;
-    for (int a = 1; a < n; a++) if (plan->matchers[(size_t)a].m > plan->matchers[(size_t)longest].m) longest = a;
+    std::vector<int> k_of;
+    if (!multi_stream_eligible(descs, n, plan, longest, k_of)) return;
     const CahMatcher& ml = plan->matchers[(size_t)longest];
-    std::vector<int> k_of((size_t)n);
-    for (int a = 0; a < n; a++) {
-        const cah_adapter_desc& d = descs[a];
-        const CahMatcher& mt = plan->matchers[(size_t)a];
-        if (d.kind != CAH_KIND_ALIGNER || !mt.scan_ok || d.wildcard_ref || d.wildcard_query) return;
-        if (mt.m < 1 || mt.m > CAH_MAX_M || mt.kacc != mt.k || mt.min_overlap != ml.min_overlap) return;
-        if (memcmp(mt.thr, ml.thr, sizeof(mt.thr)) != 0) return;
-        for (int i = 0; i <= mt.m; i++) if (mt.thr_last[i] != ml.thr_last[i]) return;
-        for (int i = 0; i < mt.m; i++) { const char c = d.sequence[i]; if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return; }
-        if (d.n_kmer_sets <= 0 || !d.kmer_sets || d.kmer_ref_wildcards || d.kmer_query_wildcards) return;
-        for (int si = 0; si < d.n_kmer_sets; si++) {
-            const cah_kmer_set& ks = d.kmer_sets[si];
-            if (!((ks.start == 0 && ks.stop == 0) || (ks.start < 0 && ks.stop == 0 && ks.start >= -255))) return;
-            for (int t = 0; t < ks.n_kmers; t++) if (!ks.kmers[t] || !*ks.kmers[t]) return;
-        }
-        k_of[(size_t)a] = mt.kacc;
-    }
     std::vector<std::string> ads;
     std::vector<std::vector<M2RefKmer>> ref;
     m2_ref_sets(descs, n, ads, ref);
-    if (!m2_build_mixed(ads, ml.thr_last, k_of.data(), ml.min_overlap, ref, mp.m2) || !mp.m2.hdr.mixed) {
+    int why = M2_REFUSED_CAPACITY;
+    if (n <= CAH_MULTI_MAX_ADAPTERS) {
+        if (m2_build_mixed(ads, ml.thr_last, k_of.data(), ml.min_overlap, ref, mp.m2, &why) && mp.m2.hdr.mixed) {
+            fill_multi_tabs(plan, n, mp);
+            mp.mixed = true;
+            mp.longest = longest;
+            return;
+        }
         memset(&mp.m2.hdr, 0, sizeof(mp.m2.hdr));
-        return;
     }
-    fill_multi_tabs(plan, n, mp);
-    mp.mixed = true;
-    mp.longest = longest;
+    // more than one table: too many adapters, or too many k-mers for the table's entries
+    if (why == M2_REFUSED_CAPACITY) build_multi_groups(plan, n, longest, k_of, ads, ref);
 }
 
 static void build_multi(const cah_adapter_desc* descs, int n, cah_plan* plan) {
@@ -786,7 +861,18 @@ static void build_multi(const cah_adapter_desc* descs, int n, cah_plan* plan) {
     // 2 adapters, 2 x 9.9 ms against 75 ms per 125 M reads); CAH_MULTI_MIN overrides the threshold
     int min_adapters = 8;
     if (const char* e = getenv("CAH_MULTI_MIN")) { const int v = atoi(e); if (v >= 2) min_adapters = v; }
-    if (n < min_adapters || n > CAH_MULTI_MAX_ADAPTERS) return;
+    if (n < min_adapters) return;
+    if (n > CAH_MULTI_MAX_ADAPTERS) {
+        // more adapters of one length than a table holds: groups of tables (up to CAH_MULTI_MAX_PLAN_ADAPTERS), no fused form
+        int longest = 0;
+        std::vector<int> k_of;
+        if (n > CAH_MULTI_MAX_PLAN_ADAPTERS || env_flag_early("CAH_NO_MULTI2") || !multi_stream_eligible(descs, n, plan, longest, k_of)) return;
+        std::vector<std::string> ads;
+        std::vector<std::vector<M2RefKmer>> ref;
+        m2_ref_sets(descs, n, ads, ref);
+        build_multi_groups(plan, n, longest, k_of, ads, ref);
+        return;
+    }
     const CahMatcher& m0 = plan->matchers[0];
     auto base2 = [](char c) -> int { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; };
     struct Item { uint64_t code; uint32_t adapter; int q; int window; };
@@ -970,13 +1056,15 @@ void cah_plan_destroy(cah_plan* plan) {
         if (dc.d_mbitmap) (void)hipFree(dc.d_mbitmap);
         if (dc.d_mscan) (void)hipFree(dc.d_mscan);
         if (dc.d_mrow) (void)hipFree(dc.d_mrow);
-        if (dc.d_m2hdr) (void)hipFree(dc.d_m2hdr);
-        if (dc.d_m2dir) (void)hipFree(dc.d_m2dir);
-        if (dc.d_m2entries) (void)hipFree(dc.d_m2entries);
-        if (dc.d_m2bitmap) (void)hipFree(dc.d_m2bitmap);
-        if (dc.d_m2prefix) (void)hipFree(dc.d_m2prefix);
-        if (dc.d_m2refbegin) (void)hipFree(dc.d_m2refbegin);
-        if (dc.d_m2reflist) (void)hipFree(dc.d_m2reflist);
+        for (M2DeviceTables& dt : dc.d_m2) {
+            if (dt.d_m2hdr) (void)hipFree(dt.d_m2hdr);
+            if (dt.d_m2dir) (void)hipFree(dt.d_m2dir);
+            if (dt.d_m2entries) (void)hipFree(dt.d_m2entries);
+            if (dt.d_m2bitmap) (void)hipFree(dt.d_m2bitmap);
+            if (dt.d_m2prefix) (void)hipFree(dt.d_m2prefix);
+            if (dt.d_m2refbegin) (void)hipFree(dt.d_m2refbegin);
+            if (dt.d_m2reflist) (void)hipFree(dt.d_m2reflist);
+        }
         if (dc.d_tiny_image[0]) (void)hipFree(dc.d_tiny_image[0]);
         if (dc.d_tiny_image[1]) (void)hipFree(dc.d_tiny_image[1]);
         for (LongDeviceCopy& ld : dc.d_long) {
@@ -1014,12 +1102,22 @@ int cah_plan_prefilter_kind(const cah_plan* plan, int32_t adapter, int32_t* out)
     return CAH_OK;
 }
 
+int cah_plan_multi_groups(const cah_plan* plan, int32_t* out) {
+    if (!plan || !out) return fail(CAH_EINVAL, "plan or out is NULL");
+    *out = plan->multi.n_tables();
+    return CAH_OK;
+}
+
 int cah_plan_multi_kind(const cah_plan* plan, int32_t read_len, int32_t* out) {
     if (!plan || !out) return fail(CAH_EINVAL, "plan or out is NULL");
     const MultiPlan& mp = plan->multi;
-    if (mp.mixed) {                                          // (no fused form behind the mixed one)
-        *out = (multi2_read_len_ok(mp.m2.hdr, read_len) && !env_flag_early("CAH_NO_MULTI2") && !env_flag_early("CAH_NO_MULTI_MIXED") &&
-                !env_flag_early("CAH_NO_MULTI")) ? CAH_MULTI_STREAM : CAH_MULTI_SEQUENTIAL;
+    if (mp.mixed) {                                          // (no fused form behind the mixed one, nor behind groups of tables)
+        bool len_ok = mp.n_tables() > 0;
+        for (int g = 0; g < mp.n_tables(); g++) len_ok = len_ok && multi2_read_len_ok(mp.tables(g).hdr, read_len);
+        bool off = env_flag_early("CAH_NO_MULTI2") || env_flag_early("CAH_NO_MULTI");
+        if (!mp.groups.empty()) off = off || env_flag_early("CAH_NO_MULTI_GROUPS");
+        if (!mp.groups_one_length) off = off || env_flag_early("CAH_NO_MULTI_MIXED");
+        *out = (len_ok && !off) ? CAH_MULTI_STREAM : CAH_MULTI_SEQUENTIAL;
         return CAH_OK;
     }
     *out = !mp.hdr.ok ? CAH_MULTI_SEQUENTIAL
@@ -1182,10 +1280,11 @@ static int64_t multi_pair_cap(const cah_plan* plan, int64_t n_reads) {
     if (limit <= 0) limit = default_pair_limit();
     // (the cell DP's work list holds pair indices as int32: the pool never has 2^31 pairs or more, whatever the knob says)
     limit = std::min<int64_t>(limit, ((int64_t)1 << 31) - 4 * CAH_M2_PAGE);
-    const int64_t A = (int64_t)plan->matchers.size();
+    // (groups of tables share the pool one after the other: the LARGEST group sizes it, not the plan's adapter count)
+    const int64_t A = (int64_t)plan->multi.largest_group((int)plan->matchers.size());
     if (limit < A) limit = A;
     const int64_t fused = std::min(n_reads * A, limit);
-    if (!plan->multi.m2.hdr.ok) return fused;               // (no streaming form for this plan: no page pool, no floor)
+    if (plan->multi.n_tables() == 0) return fused;          // (no streaming form for this plan: no page pool, no floor)
     // (one block of the streaming prefilter must always be able to run)
     const int64_t floor_pages = 2 * m2_block_reserve(A) + 2 * m2_pages_per_tile(A);
     const int64_t pages = std::min(m2_pages_worst(A, n_reads), std::max(limit / CAH_M2_PAGE, floor_pages));
@@ -1556,8 +1655,11 @@ int cah_set_deferred_errors(int on) { const int old = t_deferred_errors; t_defer
 // match_batch_impl, which sends a MIXED plan -- no fused kernels behind it -- to the per-adapter loop where it is false.
 static bool multi_streams(const MultiPlan& mp, const UniformLayout& ul, const int64_t* d_offsets, const int32_t* d_lens) {
     const bool views = ul.inner && d_lens != nullptr && d_offsets != nullptr;
-    return mp.m2.hdr.ok && ul.len > 0 && (!d_lens || (views && !env_flag("CAH_NO_MULTI2_VIEWS"))) &&
-           multi2_read_len_ok(mp.m2.hdr, ul.len) && !env_flag("CAH_NO_MULTI2");
+    if (mp.n_tables() == 0 || ul.len <= 0 || !(!d_lens || (views && !env_flag("CAH_NO_MULTI2_VIEWS"))) || env_flag("CAH_NO_MULTI2")) return false;
+    if (!mp.groups.empty() && env_flag("CAH_NO_MULTI_GROUPS")) return false;
+    for (int g = 0; g < mp.n_tables(); g++)                  // (groups of tables: every group must take the length)
+        if (!multi2_read_len_ok(mp.tables(g).hdr, ul.len)) return false;
+    return true;
 }
 
 static thread_local bool t_m2_waited_in_vain = false;     // the last failure of match_batch_multi_once was err bit 1 alone
@@ -1601,39 +1703,61 @@ static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd
     const bool views = ul.inner && d_lens != nullptr && d_offsets != nullptr;    // views inside the reads of a uniform batch
     if (multi_streams(mp, ul, d_offsets, d_lens)) {
         t_last_multi_path = CAH_MULTI_STREAM;
-        // (a mixed plan: every pair with its own adapter's length; word form, ROWS and thr_last from the longest -- the
-        // explicit-row forms of 33 / 34 characters have no pad rows for a shorter adapter: the 64-bit form serves)
-        const CahMatcher& mlong = plan->matchers[(size_t)(mp.mixed ? mp.longest : 0)];
-        // the pool: pages of CAH_M2_PAGE pairs + one header word each, inside the pair area
+        // the pool: pages of CAH_M2_PAGE pairs + one header word each, inside the pair area.  Groups of tables (MultiPlan::
+        // groups) go through it one after the other: every group's kernels run to their end before the next group's start
+        // (one stream), and cap was sized by the largest group (multi_pair_cap)
         const int64_t max_pages = ((int64_t)cap * 8) / (CAH_M2_PAGE * 8 + 4);
         uint32_t* d_page_hdr = (uint32_t*)(d_pairs + max_pages * CAH_M2_PAGE);
-        const int64_t TILE = multi2_tile_reads(), per_tile = m2_pages_per_tile(A), open_pages = 16 * CAH_M2_PAIR_CLASSES;
+        const int64_t TILE = multi2_tile_reads(), open_pages = 16 * CAH_M2_PAIR_CLASSES;
+        const int G = mp.n_tables();
         // (pairs carry the read's index in 32 bits, the prefilter counts reads in an int)
         const int64_t BLOCK = (int64_t)1 << 30;
-        bool deferred = false;
-        for (int64_t lo = 0; lo < n_reads; lo += BLOCK) {
-            const int64_t cnt = std::min(BLOCK, n_reads - lo);
+        // the gate and the rounds of a group on a block of cnt reads: pure arithmetic, asked twice -- the deferred form
+        // holds only if EVERY group qualifies, which must be known before the first group runs
+        struct Shape { int64_t grid, gate, rounds; bool ungated; };
+        auto shape_of = [&](int g, int64_t cnt) {
+            const int64_t Ag = mp.group_count(g, (int)A), per_tile = m2_pages_per_tile(Ag);
             const int64_t n_tiles = (cnt + TILE - 1) / TILE;
-            int64_t grid = std::min<int64_t>(n_tiles, pd->n_cus);
-            int64_t gate = max_pages, rounds = 1;
-            bool ungated = false;                                       // (developer builds: the test switch below)
-            if (n_tiles * per_tile + grid * open_pages > max_pages) {
+            Shape sh{std::min<int64_t>(n_tiles, pd->n_cus), max_pages, 1, false};
+            if (n_tiles * per_tile + sh.grid * open_pages > max_pages) {
                 // the batch might not fit the pool: blocks stop drawing tiles once what is in flight could fill it, and
                 // the rounds go on until the tiles are done -- `rounds` is the count for the worst case (every adapter on
                 // every read); a round that finds no tile left costs four empty launches
-                grid = std::max<int64_t>(1, std::min(grid, (max_pages / 2) / m2_block_reserve(A)));
-                gate = max_pages - grid * m2_block_reserve(A);
-                const int64_t sure = std::max<int64_t>(1, (gate - grid * open_pages) / per_tile);
-                rounds = (n_tiles + sure - 1) / sure;
+                sh.grid = std::max<int64_t>(1, std::min(sh.grid, (max_pages / 2) / m2_block_reserve(Ag)));
+                sh.gate = max_pages - sh.grid * m2_block_reserve(Ag);
+                const int64_t sure = std::max<int64_t>(1, (sh.gate - sh.grid * open_pages) / per_tile);
+                sh.rounds = (n_tiles + sure - 1) / sure;
             }
 #ifdef CAH_DEV_KNOBS
             // libcutadapt_hip_dev.so only (cutadapt_amd/build.py: build_dev_library; tests/test_gpu_multi2.py): takes the
             // gate away to provoke the pool's overflow.  The product library does not hold this switch.
-            if (env_flag("CAH_TEST_M2_UNGATED")) { gate = (int64_t)1 << 60; rounds = 1; ungated = true; }
+            if (env_flag("CAH_TEST_M2_UNGATED")) { sh.gate = (int64_t)1 << 60; sh.rounds = 1; sh.ungated = true; }
 #endif
-            HIP_TRY(hipMemsetAsync(counters, 0, WS_HEADER, s));
-            // (the pool holds the worst case of the whole batch, one launch draws every tile: nothing for the host to decide)
-            deferred = t_deferred_errors && rounds == 1 && (gate == max_pages || ungated) && n_reads <= BLOCK;
+            return sh;
+        };
+        // (the pool holds the worst case of the whole batch, one launch draws every tile: nothing for the host to decide)
+        bool deferred = t_deferred_errors && n_reads <= BLOCK;
+        for (int g = 0; g < G && deferred; g++) {
+            const Shape sh = shape_of(g, n_reads);
+            deferred = sh.rounds == 1 && (sh.gate == max_pages || sh.ungated);
+        }
+        for (int64_t lo = 0; lo < n_reads; lo += BLOCK) {
+            const int64_t cnt = std::min(BLOCK, n_reads - lo);
+            const int64_t n_tiles = (cnt + TILE - 1) / TILE;
+          for (int g = 0; g < G; g++) {
+            const M2Tables& tb = mp.tables(g);
+            const M2DeviceTables& dt = pd->d_m2[(size_t)g];
+            const int base = mp.group_base(g);
+            const int64_t Ag = mp.group_count(g, (int)A), per_tile = m2_pages_per_tile(Ag);
+            const bool g_mixed = tb.hdr.mixed != 0;
+            // (a group of different lengths: every pair with its own adapter's length; word form, ROWS and thr_last from the
+            // group's longest -- the explicit-row forms of 33 / 34 characters have no pad rows for a shorter adapter: the 64-bit
+            // form serves.  A group of one length takes the one-shape kernels with its first adapter's shape)
+            const CahMatcher& mlong = plan->matchers[(size_t)(base + mp.group_longest(g))];
+            const Shape sh = shape_of(g, cnt);
+            const int64_t grid = sh.grid, gate = sh.gate, rounds = sh.rounds;
+            // (a later group of the block keeps the error word of the groups before it: WS_M2_ERR lies behind what is zeroed)
+            HIP_TRY(hipMemsetAsync(counters, 0, g == 0 ? WS_HEADER : WS_M2_ERR * sizeof(unsigned long long), s));
           for (int64_t round = 0;; round++) {
             if (round >= rounds && deferred) break;
             if (round >= rounds) {
@@ -1646,7 +1770,7 @@ static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd
                 if (st[1])
                     return fail(CAH_EINTERNAL, "multi-adapter path: %s (pool of %lld pages, %lld adapters, %lld reads): results discarded",
                                 (st[1] & 1ull) ? "the page pool ran out" : "a wave waited in vain for its tile",
-                                (long long)max_pages, (long long)A, (long long)cnt);
+                                (long long)max_pages, (long long)Ag, (long long)cnt);
                 if ((int64_t)st[0] >= n_tiles) break;
                 // tiles are left (the worst-case round count was too small): go on, a round at a time
                 if (round >= rounds + 4 * n_tiles)
@@ -1654,56 +1778,62 @@ static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd
                                 (long long)(n_tiles - (int64_t)st[0]), (long long)n_tiles, (long long)round);
             }
             if (round) HIP_TRY(hipMemsetAsync(counters, 0, WS_M2_TILE * sizeof(unsigned long long), s));
+            // (the profile counts the batch's reads once: a further round, or a further group, is the same pass over them)
+            const int64_t units = (round || g) ? -1 : cnt;
             {
                 Multi2Args f;
                 f.uniform_first = ul.first; f.uniform_len = ul.len;
-                f.win_hi = mp.m2.hdr.win_dist[M2_HI]; f.win_lo = mp.m2.hdr.win_dist[M2_LO];
-                f.hdr = pd->d_m2hdr; f.dir = pd->d_m2dir; f.entries = pd->d_m2entries; f.bitmap = pd->d_m2bitmap;
-                f.prefix = pd->d_m2prefix;
+                f.win_hi = tb.hdr.win_dist[M2_HI]; f.win_lo = tb.hdr.win_dist[M2_LO];
+                f.hdr = dt.d_m2hdr; f.dir = dt.d_m2dir; f.entries = dt.d_m2entries; f.bitmap = dt.d_m2bitmap;
+                f.prefix = dt.d_m2prefix;
                 f.seqs = d_seqs; f.first_read = lo; f.n_reads = cnt; f.status = d_status; f.best_key = d_best_key;
                 f.pairs = d_pairs; f.page_hdr = d_page_hdr; f.page_counter = counters + WS_QCOUNT; f.max_pages = max_pages;
                 f.tile_counter = counters + WS_M2_TILE; f.n_tiles = n_tiles; f.gate_pages = gate;
                 f.err = counters + WS_M2_ERR;
                 f.wmeta = d_wmeta;
+                f.adapter_base = base;
                 if (views) { f.view_starts = d_offsets; f.view_lens = d_lens; f.view_general = ul.general ? 1 : 0; }
-                ProfScope ps(s, CAH_PROF_FILTER, round ? -1 : cnt);
-                HIP_TRY(launch_multi_stream(f, mp.m2.hdr, (int)grid, s));
+                ProfScope ps(s, CAH_PROF_FILTER, units);
+                HIP_TRY(launch_multi_stream(f, tb.hdr, (int)grid, s));
             }
             {
                 Multi2ScanArgs sa;
                 sa.uniform_first = ul.first; sa.uniform_len = ul.len;
-                sa.kind = scan_word_kind(m0.m);
-                if (mp.mixed) { sa.mixed = 1; sa.longest = mp.longest; sa.kind = scan_word_kind(mlong.m) == 1 ? 1 : 0; }
-                sa.rows_lo = mp.m2.hdr.rows_lo;
-                sa.matcher = pd->d_matchers; sa.tab = pd->d_mscan; sa.n_adapters = (int32_t)A;
+                sa.kind = scan_word_kind(mlong.m);
+                if (g_mixed) { sa.mixed = 1; sa.longest = mp.group_longest(g); sa.kind = scan_word_kind(mlong.m) == 1 ? 1 : 0; }
+                sa.rows_lo = tb.hdr.rows_lo;
+                sa.matcher = pd->d_matchers + base; sa.tab = pd->d_mscan + (size_t)base * CAH_MULTI_TAB_STRIDE; sa.n_adapters = (int32_t)Ag;
                 sa.seqs = d_seqs; sa.pairs = d_pairs; sa.page_hdr = d_page_hdr;
                 sa.page_counter = counters + WS_QCOUNT; sa.max_pages = max_pages; sa.err = counters + WS_M2_ERR;
                 sa.work_counter = counters + WS_SCANWORK; sa.best_key = d_best_key;
                 sa.dp_queue = d_dpq; sa.dp_win = d_win;
                 sa.dp_count_front = counters + WS_DPFRONT; sa.dp_count_back = counters + WS_DPBACK; sa.dp_cap = cap;
-                sa.wmeta = d_wmeta; sa.prefix = pd->d_m2prefix; sa.lmax0 = mp.m2.hdr.lmax0;
+                sa.wmeta = d_wmeta; sa.prefix = dt.d_m2prefix; sa.lmax0 = tb.hdr.lmax0;
+                sa.adapter_base = base;
                 if (views) { sa.view_starts = d_offsets; sa.view_lens = d_lens; sa.view_general = ul.general ? 1 : 0; }
                 // (how many pages there are is known on the device only: the blocks draw pages until none is left)
-                ProfScope ps(s, CAH_PROF_SCAN, round ? -1 : cnt);
+                ProfScope ps(s, CAH_PROF_SCAN, units);
                 HIP_TRY(launch_multi_scan(sa, std::min(max_pages, n_tiles * per_tile + grid * open_pages), pd->n_cus, s));
             }
             {
                 // the cell DP over the pairs the scan left (the launch returns at once when there are none)
                 DpArgs a;
                 a.uniform_first = ul.first; a.uniform_len = views ? 0 : ul.len;     // (views: the cell DP reads starts + lengths)
-                a.matcher = pd->d_matchers;
-                a.seqs = d_seqs; a.offsets = d_offsets; a.lens = d_lens; a.n_reads = cnt * A;
+                a.matcher = pd->d_matchers + base;
+                a.seqs = d_seqs; a.offsets = d_offsets; a.lens = d_lens; a.n_reads = cnt * Ag;
                 a.max_read_len = CAH_MAX_READ_LEN;
                 a.queue_keys = nullptr;
                 a.out6 = d_out6; a.status = d_status; a.best_adapter = d_best_adapter;
                 a.adapter_index = 0; a.merge_best = 1;
-                a.pairs = d_pairs; a.tab = pd->d_mrow; a.n_adapters = (int32_t)A; a.best_key = d_best_key;
+                a.pairs = d_pairs; a.tab = pd->d_mrow + (size_t)base * CAH_MULTI_TAB_STRIDE; a.n_adapters = (int32_t)Ag; a.best_key = d_best_key;
                 a.queue = d_dpq; a.queue_count = counters + WS_DPFRONT; a.queue_count_back = counters + WS_DPBACK;
                 a.win = d_win; a.queue_cap = cap; a.work_counter = counters + WS_DPWORK;
-                a.m2_hdr = pd->d_m2hdr; a.m2_ref_begin = pd->d_m2refbegin; a.m2_ref_list = pd->d_m2reflist;
-                ProfScope ps(s, CAH_PROF_DP, round ? -1 : cnt);
-                HIP_TRY(launch_dp(a, mlong.m, true, true, std::min(cap, cnt * A), pd->n_cus, s, mp.mixed));
+                a.m2_hdr = dt.d_m2hdr; a.m2_ref_begin = dt.d_m2refbegin; a.m2_ref_list = dt.d_m2reflist;
+                a.adapter_base = base;
+                ProfScope ps(s, CAH_PROF_DP, units);
+                HIP_TRY(launch_dp(a, mlong.m, true, true, std::min(cap, cnt * Ag), pd->n_cus, s, g_mixed));
             }
+          }
           }
         }
         ProfScope ps(s, CAH_PROF_MERGE, n_reads);
@@ -1794,8 +1924,9 @@ static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const i
     // long reads of 16..160 characters, or views / frames of such a length; anything else is the per-adapter loop below
     // (the layout match_batch_multi gets below: views keep theirs, a suffix-only layout is no uniform batch for it)
     const UniformLayout ul_multi = (ul_in.inner && d_lens) ? ul_in : (ul_in.suffix ? UniformLayout() : ul_in);
+    // (groups of tables, build_multi_groups, are routed the same way: multi_streams asks every group and CAH_NO_MULTI_GROUPS)
     const bool mixed_go = plan->multi.mixed && ws_multi && multi_streams(plan->multi, ul_multi, (const int64_t*)d_offsets, d_lens) &&
-                          !env_flag("CAH_NO_MULTI_MIXED") && !env_flag("CAH_NO_MULTI");
+                          !(env_flag("CAH_NO_MULTI_MIXED") && !plan->multi.groups_one_length) && !env_flag("CAH_NO_MULTI");
     const UniformLayout ul = (ul_in.general && multi_form &&
                               !(plan->multi.m2.hdr.ok && multi2_read_len_ok(plan->multi.m2.hdr, ul_in.len) && !env_flag("CAH_NO_MULTI2") &&
                                 !env_flag("CAH_NO_MULTI2_VIEWS")))

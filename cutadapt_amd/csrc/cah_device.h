@@ -142,7 +142,8 @@ struct CahLeanFilter {
 // (HBM/L2) to the entries of that key; an entry is verified against the read's rolling 2-bit code
 // (all q characters, search window) before the (read, adapter) pair is emitted.
 // ---------------------------------------------------------------------------------------------
-#define CAH_MULTI_MAX_ADAPTERS 128      // per fused class pass (per-lane "already emitted" bitset: 16 B of LDS)
+#define CAH_MULTI_MAX_ADAPTERS 128      // per fused class pass (per-lane "already emitted" bitset: 16 B of LDS) = per TABLE SET of the
+                                        // streaming form; a plan of up to CAH_MULTI_MAX_PLAN_ADAPTERS (multi2.h) is several such sets
 #define CAH_MULTI_CLASSES 9             // index 1..8 used
 #define CAH_MULTI_TAB 32                // per-adapter match table: index = read character & 31 (letters only)
 

@@ -90,6 +90,9 @@ struct DpArgs {
     const struct CahMulti2Header* m2_hdr = nullptr;
     const int32_t* m2_ref_begin = nullptr;
     const uint32_t* m2_ref_list = nullptr;
+    // Groups of tables (multi2.h: m2_build_groups): the pairs' adapters, matcher, tab and m2_ref_begin are those of ONE
+    // group; the adapter a match is merged under (pack_best) is the pair's + adapter_base, the plan's index
+    int32_t adapter_base = 0;
 };
 // launch_dp's ROWS of a mixed multi-adapter plan (k_dp_packed<ROWS, true, true>: fewer sizes than the one-shape kernels have)
 inline int dp_mixed_rows(int m) { return m <= 24 ? 24 : (m <= 32 ? 32 : (m <= 48 ? 48 : 64)); }
@@ -256,6 +259,9 @@ struct Multi2Args {
     // 1: the views lie ANYWHERE in seqs (a packed batch with its offsets, the reads of a raw FASTQ chunk): no read around
     // them, uniform_len is the frame's length alone (>= every view's); the copy gathers every unit from its view's end
     int32_t view_general = 0;
+    // groups of tables (multi2.h: m2_build_groups): hdr .. prefix are ONE group's, whose adapter 0 is the plan's adapter
+    // adapter_base -- added wherever an adapter goes into a best key (pack_best), nowhere else
+    int32_t adapter_base = 0;
 };
 struct Multi2ScanArgs {
     int64_t uniform_first;
@@ -290,6 +296,9 @@ struct Multi2ScanArgs {
     // thr_last from matcher[longest]; kind is 0 or 1
     int32_t mixed = 0;
     int32_t longest = 0;
+    // groups of tables: matcher, tab and prefix are ONE group's (longest: its index inside the group); the adapter of a
+    // best key is the pair's + adapter_base
+    int32_t adapter_base = 0;
 };
 bool multi2_read_len_ok(const CahMulti2Header& h, int read_len);
 size_t multi2_lds_bytes(const CahMulti2Header& h);

@@ -1725,7 +1725,7 @@ __global__ __launch_bounds__(256, CAH_DPP_WAVES(ROWS)) void k_dp_packed(DpArgs a
                     merge = m2_ref_present(a.m2_ref_list, a.m2_ref_begin[adapter], a.m2_ref_begin[adapter + 1], q, n, a.m2_hdr->ref_span);
             }
             if (merge)
-                atomicMax(a.best_key + r, pack_best(b_score, b_cost, (int)adapter, b_refstop, max(b_origin, 0), b_qstop));
+                atomicMax(a.best_key + r, pack_best(b_score, b_cost, (int)adapter + a.adapter_base, b_refstop, max(b_origin, 0), b_qstop));
         } else if (valid) {
             const bool found = b_cost != SENT && !invalid;
             store_result(a.out6, a.status, a.best_adapter, a.adapter_index, a.merge_best, r, invalid, found,

@@ -238,6 +238,7 @@ M2_HD bool m2_ref_present(const uint32_t* list, int begin, int end, const uint8_
 
 #if !defined(CAH_M2_NO_HOST)
 #include <algorithm>
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -284,11 +285,21 @@ inline std::vector<std::string> m2_chunks(const std::string& s, int chunks) {
 // sub-class that begins behind an adapter's last row adds no entry): the set of k-mer lengths -- the passes and mask
 // registers -- is what a plan of the longest length alone has.  Conditions (i), (iii), (iv) are checked per adapter
 // against that adapter's own reference sets, (iv) with windows that reach min(lmax_e, its length).
+// Why a builder returned false (its optional last argument): CAPACITY -- the adapters are too many for ONE table (more than
+// CAH_M2_MAX_ENTRIES k-mer entries, an adapter or chain number of 128 or more) and fewer of them may fit: m2_build_groups
+// cuts such a set in two.  RULE -- anything else (thresholds, lmax0 > CAH_M2_MAXQ, passes or mask registers, the search
+// sets' properties (i) / (iii) / (iv), not plain ACGT): no subset of the adapters fares better.
+enum { M2_REFUSED_NOT = 0, M2_REFUSED_CAPACITY = 1, M2_REFUSED_RULE = 2 };
+
 inline bool m2_build_impl(const std::vector<std::string>& adapters, const int32_t* thr_last, const int* k_of, int min_overlap,
-                          const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t) {
+                          const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t, int* why = nullptr) {
     CahMulti2Header& h = t.hdr;
     h = CahMulti2Header();
     const int A = (int)adapters.size();
+    int why_local = M2_REFUSED_RULE;
+    int& reason = why ? *why : why_local;
+    reason = M2_REFUSED_RULE;                                           // (every return below but the three that say otherwise)
+    if (A > 128) reason = M2_REFUSED_CAPACITY;
     if (A < 1 || A > 128) return false;
     int m = 0, k = 0, m_min = 1 << 20;
     for (int a = 0; a < A; a++) {
@@ -438,7 +449,7 @@ inline bool m2_build_impl(const std::vector<std::string>& adapters, const int32_
         const bool fixed = e.cls == M2_SHORT && e.dlo == q && e.dhi == q && q <= CAH_M2_FIXED_MAXQ;
         if (fixed) {
             // (the adapters of a string in ascending order: head in the table, then the chain)
-            if (e.adapter >= 128) return false;
+            if (e.adapter >= 128) { reason = M2_REFUSED_CAPACITY; return false; }
             uint8_t* at = &fixed_tab[m2_fixed_off(q) + (code & m2_mask2(q))];
             while (*at != 0xFFu && *at < e.adapter) at = &fixed_tab[m2_fixed_next(q) + *at];
             if (*at != (uint8_t)e.adapter) {
@@ -475,7 +486,7 @@ inline bool m2_build_impl(const std::vector<std::string>& adapters, const int32_
         } else if (e.cls != M2_W) nonfixed_mask[e.cls] |= 1 << qc;
         if (e.cls == M2_HI || e.cls == M2_LO) h.win_dist[e.cls] = std::max(h.win_dist[e.cls], e.dhi + 1);
     }
-    if (placed.size() > CAH_M2_MAX_ENTRIES) return false;
+    if (placed.size() > CAH_M2_MAX_ENTRIES) { reason = M2_REFUSED_CAPACITY; return false; }
     h.n_entries = (uint32_t)placed.size();
     std::stable_sort(placed.begin(), placed.end(), [](const Placed& x, const Placed& y) { return x.home < y.home; });
     t.entries.clear();
@@ -526,6 +537,7 @@ inline bool m2_build_impl(const std::vector<std::string>& adapters, const int32_
         t.prefix[(size_t)a] = p;
     }
     h.ok = 1;
+    reason = M2_REFUSED_NOT;
     return true;
 }
 
@@ -535,12 +547,13 @@ inline bool m2_build_impl(const std::vector<std::string>& adapters, const int32_
 // non-monotone thresholds, an error-free class longer than a word, or search sets without the properties (i), (iii),
 // (iv) of this file's head.
 inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* thr_last, int kacc, int k, int min_overlap,
-                     const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t) {
+                     const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t, int* why = nullptr) {
     t.hdr = CahMulti2Header();
+    if (why) *why = M2_REFUSED_RULE;
     if (adapters.empty() || kacc < 0 || kacc != k) return false;
     for (const std::string& ad : adapters) if (ad.size() != adapters[0].size()) return false;
     const std::vector<int> k_of(adapters.size(), kacc);
-    return m2_build_impl(adapters, thr_last, k_of.data(), min_overlap, ref, t);
+    return m2_build_impl(adapters, thr_last, k_of.data(), min_overlap, ref, t, why);
 }
 
 // The MIXED form: adapters of different lengths that share one min_overlap and agree on thr_last row by row (one
@@ -551,13 +564,84 @@ inline bool m2_build(const std::vector<std::string>& adapters, const int32_t* th
 // prefix).  Rates below 1 / 11 are out for either builder: lmax0 would pass the ten characters of that compare, and the
 // chunks of the first error class the ten of a table key (CAH_M2_MAXQ).
 inline bool m2_build_mixed(const std::vector<std::string>& adapters, const int32_t* thr_last, const int* k_of, int min_overlap,
-                           const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t) {
+                           const std::vector<std::vector<M2RefKmer>>& ref, M2Tables& t, int* why = nullptr) {
     t.hdr = CahMulti2Header();
+    if (why) *why = M2_REFUSED_RULE;
     if (min_overlap < 1) return false;
     for (const std::string& ad : adapters) if ((int)ad.size() < min_overlap || ad.size() > 64) return false;
-    if (!m2_build_impl(adapters, thr_last, k_of, min_overlap, ref, t)) return false;
+    if (!m2_build_impl(adapters, thr_last, k_of, min_overlap, ref, t, why)) return false;
     for (const std::string& ad : adapters)
-        if ((int)ad.size() < t.hdr.lmax0) { t.hdr.ok = 0; return false; }
+        if ((int)ad.size() < t.hdr.lmax0) { t.hdr.ok = 0; if (why) *why = M2_REFUSED_RULE; return false; }
+    return true;
+}
+
+// GROUPS of tables: a plan of more adapters than one table holds -- more than 128, or more k-mer entries than
+// CAH_M2_MAX_ENTRIES -- as several tables over CONTIGUOUS ranges of the plan's adapters, group g = [base, base + count).
+// Every group goes through the same kernels against the same per-read best key; the kernels add the group's base to the
+// adapter they put into a key (kernels.h: pack_best gives the adapter 12 bits), so one decode behind the last group gives
+// MultipleAdapters' answer (higher score, fewer errors, first adapter; adapters.py:1265-1286) whatever the groups' order.
+// Inside a group everything is group-local: the entries' adapter numbers, the chains, prefix[], ref_begin[].
+//   * the cut by count comes first: ceil(n / 128) groups of nearly equal size (129 adapters: 65 + 64, never 128 + 1);
+//   * a group's table is the existing builders', unchanged: m2_build for a group of one length, m2_build_mixed otherwise
+//     (thr_last: the PLAN's longest adapter's -- the adapters agree on it row by row; k_of[a]: kacc of adapter a);
+//   * a group refused for CAPACITY is cut in two halves and tried again, down to 8 adapters per group; a group refused for
+//     a RULE refuses the plan (no subset fares better), and so does a group that cannot be halved any more.
+// `fits` (optional) lets the caller turn a built group down as too large; it is halved like a group refused for capacity.
+// A plan that fits one table gives one group with exactly that table.  A plan of different lengths must pass
+// m2_build_mixed's own conditions as a WHOLE (min_overlap >= 1, no adapter shorter than it or than the error-free rows),
+// although a group of it may be of one length.
+#define CAH_MULTI_MAX_PLAN_ADAPTERS 1024
+#define CAH_M2_MIN_GROUP 8
+struct M2Group { int base, count; M2Tables t; };
+
+inline bool m2_build_groups(const std::vector<std::string>& adapters, const int32_t* thr_last, const int* k_of, int min_overlap,
+                            const std::vector<std::vector<M2RefKmer>>& ref, std::vector<M2Group>& groups, int* why = nullptr,
+                            const std::function<bool(const M2Tables&)>& fits = nullptr) {
+    groups.clear();
+    int why_local;
+    int& reason = why ? *why : why_local;
+    reason = M2_REFUSED_RULE;
+    const int n = (int)adapters.size();
+    if (n < 1 || n > CAH_MULTI_MAX_PLAN_ADAPTERS) { if (n > CAH_MULTI_MAX_PLAN_ADAPTERS) reason = M2_REFUSED_CAPACITY; return false; }
+    bool plan_mixed = false;
+    for (const std::string& ad : adapters) plan_mixed = plan_mixed || ad.size() != adapters[0].size();
+    if (plan_mixed) {
+        if (min_overlap < 1) return false;
+        int longest = 0, lmax0 = 0;
+        for (const std::string& ad : adapters) longest = std::max(longest, (int)std::min<size_t>(ad.size(), 64));
+        for (int i = min_overlap; i <= longest && thr_last[i] == 0; i++) lmax0 = i;   // (thr_last is monotone where a table is built)
+        for (const std::string& ad : adapters)
+            if ((int)ad.size() < min_overlap || ad.size() > 64 || (int)ad.size() < lmax0) return false;
+    }
+    std::vector<std::pair<int, int>> todo;                              // (base, count), the next range last
+    const int g0 = (n + 127) / 128;
+    for (int g = g0 - 1; g >= 0; g--) {
+        const int b = (int)((int64_t)n * g / g0), e = (int)((int64_t)n * (g + 1) / g0);
+        todo.push_back({b, e - b});
+    }
+    while (!todo.empty()) {
+        const int base = todo.back().first, count = todo.back().second;
+        todo.pop_back();
+        const std::vector<std::string> ads(adapters.begin() + base, adapters.begin() + base + count);
+        const std::vector<std::vector<M2RefKmer>> rf(ref.begin() + base, ref.begin() + base + count);
+        bool one_length = true;
+        for (const std::string& ad : ads) one_length = one_length && ad.size() == ads[0].size();
+        groups.push_back(M2Group());
+        M2Group& gr = groups.back();
+        gr.base = base; gr.count = count;
+        int r = M2_REFUSED_RULE;
+        const bool ok = one_length ? m2_build(ads, thr_last, k_of[base], k_of[base], min_overlap, rf, gr.t, &r)
+                                   : m2_build_mixed(ads, thr_last, k_of + base, min_overlap, rf, gr.t, &r);
+        // (fits: what the caller's kernels hold beyond the table's own limits -- api.cpp: the prefilter's LDS, which grows
+        // with entries and adapters; a group that is built but does not fit is too large, like one refused for capacity)
+        if (ok && (!fits || fits(gr.t))) continue;
+        if (ok) r = M2_REFUSED_CAPACITY;
+        groups.pop_back();
+        if (r != M2_REFUSED_CAPACITY || count / 2 < CAH_M2_MIN_GROUP) { groups.clear(); reason = r; return false; }
+        todo.push_back({base + count / 2, count - count / 2});
+        todo.push_back({base, count / 2});
+    }
+    reason = M2_REFUSED_NOT;
     return true;
 }
 #endif

@@ -559,7 +559,7 @@ __global__ __launch_bounds__(M2_WAVES * WAVE) void k_multi_stream(Multi2Args a) 
             if (mine && pc == 7) {
                 const int adapter = (int)((st.x >> 8) & 255u);
                 const int i = m2_exact_tail(s_rlast[lr2], s_prefix[adapter], min_overlap, lmax0, n);
-                if (i > 0) atomicMax(a.best_key + st.y, pack_best(i, 0, adapter, i, nv2 - i, nv2));
+                if (i > 0) atomicMax(a.best_key + st.y, pack_best(i, 0, adapter + a.adapter_base, i, nv2 - i, nv2));
             }
             unsigned long long em = __ballot(mine && pc != 7);
             const uint64_t pair = ((uint64_t)st.y << 32) | (uint64_t)(st.x & 0x0FFFFFFFu);
@@ -959,7 +959,7 @@ __global__ __launch_bounds__(M2_WAVES * WAVE) void k_multi_stream(Multi2Args a) 
                         if (taken) adapter = s_fixed[m2_fixed_next(q) + adapter];
                     }
                     if (adapter != 0xFFu) {
-                        const unsigned long long kk = pack_best(q, 0, (int)adapter, q, n - skip - q, n - skip);
+                        const unsigned long long kk = pack_best(q, 0, (int)adapter + a.adapter_base, q, n - skip - q, n - skip);
                         bestk = kk > bestk ? kk : bestk;
                     }
                 }
@@ -1330,7 +1330,7 @@ __global__ __launch_bounds__(256, (KIND == 3 || KIND == 0) ? 4 : 5) void k_multi
                 bool in_pad = false;
                 auto shortcut = [&](const int score, const int errors, const int ref_stop, const int qs, const int qe) {
                     if (qs < pad) in_pad = true;
-                    else atomicMax(a.best_key + r, pack_best(score, errors, (int)adapter, ref_stop, qs - pad, qe - pad));
+                    else atomicMax(a.best_key + r, pack_best(score, errors, (int)adapter + a.adapter_base, ref_stop, qs - pad, qe - pad));
                 };
                 if (cls == BS_EXACT_FULL) shortcut(p.m, 0, p.m, o0 - p.m, o0);
                 else if (cls == BS_EXACT_TAIL) shortcut(o0 - 2 * o1, o1, o0, n - o0, n);
@@ -1338,7 +1338,7 @@ __global__ __launch_bounds__(256, (KIND == 3 || KIND == 0) ? 4 : 5) void k_multi
                 else if (cls == BS_INDEL1_FULL)
                     shortcut(p.m - 2 * (o1 >> 1) - (o1 & 1), o1 >> 1, p.m, o0 - p.m + ((o1 & 1) ? 1 : -1), o0);
                 else if (cls == BS_NONE && stopped && tail0 > 0)
-                    atomicMax(a.best_key + r, pack_best((int)tail0, 0, (int)adapter, (int)tail0, n - pad - (int)tail0, n - pad));
+                    atomicMax(a.best_key + r, pack_best((int)tail0, 0, (int)adapter + a.adapter_base, (int)tail0, n - pad - (int)tail0, n - pad));
                 if (in_pad) { cls = BS_DP; o0 = 0; o1 = 2 * n + 1; }
                 if (cls == BS_DP && pad > 0) {
                     // (the cell DP sees the view: the window's columns moved by the pad)

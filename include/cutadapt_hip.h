@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define CAH_ABI_VERSION 5   /* 2: CAH_PROF_N = 5, plan workspaces (cah_plan_workspace_bytes), no adapter length limit; 3: cah_plan_multi_kind; 4: cah_build_id, cah_last_multi_path, CAH_EINTERNAL; 5: cah_match_batch_frames, cah_set_deferred_errors, CAH_STATUS_INTERNAL, cah_mark_reads_device, cah_revcomp_in_place_device, cah_fastq_format_suffix_device, cah_info_format_device */
+#define CAH_ABI_VERSION 5   /* 2: CAH_PROF_N = 5, plan workspaces (cah_plan_workspace_bytes), no adapter length limit; 3: cah_plan_multi_kind; 4: cah_build_id, cah_last_multi_path, CAH_EINTERNAL; 5: cah_match_batch_frames, cah_set_deferred_errors, CAH_STATUS_INTERNAL, cah_mark_reads_device, cah_revcomp_in_place_device, cah_fastq_format_suffix_device, cah_info_format_device; still 5 with cah_plan_multi_groups: an added entry point, nothing that existed changed -- a caller built against 5 runs as before */
 
 /* status codes */
 #define CAH_OK 0
@@ -140,16 +140,26 @@ int cah_plan_prefilter_kind(const cah_plan *plan, int32_t adapter, int32_t *out)
 /* how a batch of equally long reads of `read_len` characters is matched against ALL adapters of the plan
  * (MultipleAdapters.match_to, adapters.py:1265-1286): one adapter after the other, one fused prefilter pass over
  * (read, adapter) pairs, or its streaming form (k_multi_stream: LDS-staged reads, pairs in pages by window class).
- * Adapters of DIFFERENT lengths (the mixed form): 8..128 plain-ACGT 3' adapters, all scan-eligible, one min_overlap and
+ * Adapters of DIFFERENT lengths (the mixed form): 8..1024 plain-ACGT 3' adapters, all scan-eligible, one min_overlap and
  * one max_error_rate (thresholds that agree row by row -- a plan from absolute max_errors does not), answer STREAM for
  * the read lengths the streaming kernels take (16..160, less where the longest adapter's tail windows reach further back
  * than the last half-row of the read that the prefilter keeps in LDS) and SEQUENTIAL otherwise: there is no fused form behind the mixed one.  It needs
  * 8 adapters whatever CAH_MULTI_MIN says (CAH_MULTI_MIXED_MIN >= 2 lowers that for experiments); CAH_NO_MULTI_MIXED=1
- * turns it off (so do CAH_NO_MULTI and CAH_NO_MULTI2): such a plan then takes the per-adapter loop. */
+ * turns it off (so do CAH_NO_MULTI and CAH_NO_MULTI2): such a plan then takes the per-adapter loop.
+ * GROUPS of tables: one table set of the streaming form holds 128 adapters and 2 304 k-mer entries.  A plan of 129..1024
+ * such adapters -- of one length or mixed --, and a mixed plan of up to 128 whose k-mers do not fit (96 adapters at rate
+ * 0.2), is cut into contiguous groups of at most 128 adapters with a table set each; a batch goes through every group's
+ * kernels against the same per-read best keys (the kernels merge under the adapter's index in the PLAN), one decode
+ * behind the last group.  Such a plan answers STREAM where every group takes the read length and SEQUENTIAL otherwise
+ * (no fused form behind it); CAH_NO_MULTI_GROUPS=1, asked at every call, sends it to the per-adapter loop.  More than
+ * 1024 adapters take the loop as before. */
 #define CAH_MULTI_SEQUENTIAL 0
 #define CAH_MULTI_FUSED 1
 #define CAH_MULTI_STREAM 2
 int cah_plan_multi_kind(const cah_plan *plan, int32_t read_len, int32_t *out);
+/* table sets of the streaming form a batch of this plan goes through: 0 -- the plan has no streaming tables --, 1, or
+ * the number of groups of a grouped plan (above) */
+int cah_plan_multi_groups(const cah_plan *plan, int32_t *out);
 /* the form the calling thread's LAST cah_match_batch / cah_match_batch_uniform call actually took (one of the three
  * above; -1 before the first call): cah_plan_multi_kind says what a plan can do for a read length, this says what ran
  * -- a ragged batch or a workspace smaller than cah_plan_workspace_bytes falls back without an error */
