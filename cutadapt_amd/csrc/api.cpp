@@ -28,6 +28,7 @@
 #include "cah_device.h"
 #include "kernels.h"
 #include "multi2.h"
+#include "multi_route.h"
 #include "back_scan.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -130,13 +131,20 @@ bool kmer_chars_match(uint8_t rc, uint8_t qc, bool ref_wc, bool query_wc) {
     return (t.iupac[rc] & t.iupac[qc]) != 0;
 }
 
-bool env_flag_early(const char* name) { const char* e = getenv(name); return e && *e && *e != '0'; }
+// an environment switch: set, not empty, not "0..."
+bool env_flag(const char* name) { const char* e = getenv(name); return e && *e && *e != '0'; }
 
 // CAH_NO_SCAN=1 (read at plan creation): the plan is built without the cost scan (A/B measurements,
 // parity tests of the scan against the plain cell kernel)
-bool scan_disabled() {
-    const char* e = getenv("CAH_NO_SCAN");
-    return e && *e && *e != '0';
+bool scan_disabled() { return env_flag("CAH_NO_SCAN"); }
+
+// the multi-adapter path's switches as a call finds them (read per call: tests and A/B runs flip them inside one process)
+MultiSwitches multi_switches() {
+    MultiSwitches sw;
+    sw.no_multi = env_flag("CAH_NO_MULTI"); sw.no_multi2 = env_flag("CAH_NO_MULTI2");
+    sw.no_multi2_views = env_flag("CAH_NO_MULTI2_VIEWS"); sw.no_multi_mixed = env_flag("CAH_NO_MULTI_MIXED");
+    sw.no_multi_groups = env_flag("CAH_NO_MULTI_GROUPS");
+    return sw;
 }
 
 int clamp_floor(double x) {
@@ -183,7 +191,7 @@ struct PlanDeviceCopy {
     CahMatcher* d_matchers = nullptr;     // HBM
     CahKmerWord* d_words = nullptr;
     CahLeanFilter* d_lean = nullptr;      // one per matcher (ok = 0 where the lean prefilter does not apply)
-    // fused multi-adapter path (hdr.ok only)
+    // fused multi-adapter path (M_ONE_SHAPE only)
     CahMultiHeader* d_mhdr = nullptr;
     CahMultiDir* d_mdir = nullptr;
     CahMultiEntry* d_mentries = nullptr;
@@ -195,39 +203,6 @@ struct PlanDeviceCopy {
     std::vector<LongDeviceCopy> d_long;   // one per matcher (null pointers for bare k-mer finders)
     // the one-read kernel's table images ([0]: Aligner.locate, no prefilter; [1]: match_to), built by its first call
     void* d_tiny_image[2] = {nullptr, nullptr};
-};
-
-// host tables of the fused multi-adapter path (see CahMultiHeader)
-struct MultiPlan {
-    CahMultiHeader hdr;
-    std::vector<CahMultiDir> dir;
-    std::vector<CahMultiEntry> entries;
-    std::vector<uint32_t> bitmap;
-    std::vector<uint64_t> scan_tab, row_tab;
-    M2Tables m2;                          // the streaming form's tables (m2.hdr.ok: equally long short reads take it)
-    // The MIXED form (build_multi_mixed): adapters of different lengths.  hdr.ok stays 0 -- the older fused kernels are
-    // one-shape --, m2 holds m2_build_mixed's tables, scan_tab / row_tab are filled; a batch the streaming form cannot
-    // take goes through the per-adapter loop
-    bool mixed = false;
-    int longest = 0;                      // the (first) longest adapter: word form, ROWS and thr_last come from it
-    // GROUPS of tables (build_multi_groups; multi2.h: m2_build_groups): a plan of more adapters than one table holds.
-    // hdr.ok and m2.hdr.ok stay 0, `mixed` is set -- like a mixed plan it has no fused form behind it --, every group has
-    // tables of its own over the adapters [base, base + count); scan_tab / row_tab are the plan's, indexed from base
-    struct Group { int base = 0, count = 0, longest = 0; M2Tables m2; };   // longest: the group's, as an index INSIDE it
-    std::vector<Group> groups;
-    bool groups_one_length = false;       // a grouped plan whose adapters are all equally long (CAH_NO_MULTI_MIXED does not mean it)
-    MultiPlan() { memset(&hdr, 0, sizeof(hdr)); memset(&m2.hdr, 0, sizeof(m2.hdr)); }
-    // the table sets a batch goes through, in order: the groups', or the one of a plan that fits a table (none: no streaming form)
-    int n_tables() const { return !groups.empty() ? (int)groups.size() : (m2.hdr.ok ? 1 : 0); }
-    const M2Tables& tables(int g) const { return groups.empty() ? m2 : groups[(size_t)g].m2; }
-    int group_base(int g) const { return groups.empty() ? 0 : groups[(size_t)g].base; }
-    int group_count(int g, int n_plan) const { return groups.empty() ? n_plan : groups[(size_t)g].count; }
-    int group_longest(int g) const { return groups.empty() ? (mixed ? longest : 0) : groups[(size_t)g].longest; }
-    int largest_group(int n_plan) const {
-        int c = groups.empty() ? n_plan : 0;
-        for (const Group& g : groups) c = std::max(c, g.count);
-        return c;
-    }
 };
 
 // Host tables are built (and validated) at creation; the HBM copy for a device is made the
@@ -280,11 +255,11 @@ static int plan_on_device(const cah_plan* plan, const PlanDeviceCopy** out) {
             HIP_TRY(hipMemcpy(ld.d_ncnt, lt.ncnt.data(), sizeof(int32_t) * lt.ncnt.size(), hipMemcpyHostToDevice));
         }
         const MultiPlan& mp = plan->multi;
-        if (mp.hdr.ok || mp.mixed) {
+        if (mp.form != M_NONE) {
 #define CAH_UPLOAD(dst, vec)                                                                              \
             HIP_TRY(hipMalloc((void**)&(dst), sizeof((vec)[0]) * std::max<size_t>((vec).size(), 1)));      \
             if (!(vec).empty()) HIP_TRY(hipMemcpy((dst), (vec).data(), sizeof((vec)[0]) * (vec).size(), hipMemcpyHostToDevice));
-            if (mp.hdr.ok) {
+            if (mp.form == M_ONE_SHAPE) {
                 HIP_TRY(hipMalloc((void**)&dc.d_mhdr, sizeof(CahMultiHeader)));
                 HIP_TRY(hipMemcpy(dc.d_mhdr, &mp.hdr, sizeof(CahMultiHeader), hipMemcpyHostToDevice));
                 CAH_UPLOAD(dc.d_mdir, mp.dir)
@@ -757,26 +732,19 @@ static void m2_ref_sets(const cah_adapter_desc* descs, int n, std::vector<std::s
 // What the mixed form and the groups of tables ask of a WHOLE plan: plain-ACGT 3' adapters that are all scan-eligible
 // with kacc == k, share one min_overlap and agree on thr[] and, row by row, on thr_last[]; search sets that are whole-read
 // or tail sets.  longest: the (first) longest adapter; k_of[a] = kacc of adapter a.
+// (the matchers' half of the question is multi_route.h's, shared with the host model)
 static bool multi_stream_eligible(const cah_adapter_desc* descs, int n, const cah_plan* plan, int& longest, std::vector<int>& k_of) {
-    longest = 0;
-    for (int a = 1; a < n; a++) if (plan->matchers[(size_t)a].m > plan->matchers[(size_t)longest].m) longest = a;
-    const CahMatcher& ml = plan->matchers[(size_t)longest];
-    k_of.assign((size_t)n, 0);
+    if (!m2_matchers_eligible(plan->matchers.data(), n, longest, k_of)) return false;
     for (int a = 0; a < n; a++) {
         const cah_adapter_desc& d = descs[a];
-        const CahMatcher& mt = plan->matchers[(size_t)a];
-        if (d.kind != CAH_KIND_ALIGNER || !mt.scan_ok || d.wildcard_ref || d.wildcard_query) return false;
-        if (mt.m < 1 || mt.m > CAH_MAX_M || mt.kacc != mt.k || mt.min_overlap != ml.min_overlap) return false;
-        if (memcmp(mt.thr, ml.thr, sizeof(mt.thr)) != 0) return false;
-        for (int i = 0; i <= mt.m; i++) if (mt.thr_last[i] != ml.thr_last[i]) return false;
-        for (int i = 0; i < mt.m; i++) { const char c = d.sequence[i]; if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return false; }
+        if (d.kind != CAH_KIND_ALIGNER || d.wildcard_ref || d.wildcard_query) return false;
+        for (int i = 0; i < plan->matchers[(size_t)a].m; i++) { const char c = d.sequence[i]; if (c != 'A' && c != 'C' && c != 'G' && c != 'T') return false; }
         if (d.n_kmer_sets <= 0 || !d.kmer_sets || d.kmer_ref_wildcards || d.kmer_query_wildcards) return false;
         for (int si = 0; si < d.n_kmer_sets; si++) {
             const cah_kmer_set& ks = d.kmer_sets[si];
             if (!((ks.start == 0 && ks.stop == 0) || (ks.start < 0 && ks.stop == 0 && ks.start >= -255))) return false;
             for (int t = 0; t < ks.n_kmers; t++) if (!ks.kmers[t] || !*ks.kmers[t]) return false;
         }
-        k_of[(size_t)a] = mt.kacc;
     }
     return true;
 }
@@ -808,10 +776,8 @@ static void build_multi_groups(cah_plan* plan, int n, int longest, const std::ve
     }
     memset(&mp.m2.hdr, 0, sizeof(mp.m2.hdr));
     fill_multi_tabs(plan, n, mp);
-    mp.mixed = true;                                          // (routing: no fused form behind the groups)
+    mp.form = M_GROUPS;
     mp.longest = longest;
-    mp.groups_one_length = true;
-    for (int a = 1; a < n; a++) mp.groups_one_length = mp.groups_one_length && plan->matchers[(size_t)a].m == plan->matchers[0].m;
 }
 
 // The MIXED form of the streaming multi-adapter path: 8..128 plain-ACGT 3' adapters of DIFFERENT lengths in ONE table
@@ -825,7 +791,7 @@ static void build_multi_groups(cah_plan* plan, int n, int longest, const std::ve
 // and CAH_NO_MULTI2=1 turn it off.
 static void build_multi_mixed(const cah_adapter_desc* descs, int n, cah_plan* plan) {
     MultiPlan& mp = plan->multi;
-    if (env_flag_early("CAH_NO_MULTI_MIXED") || env_flag_early("CAH_NO_MULTI2")) return;
+    if (env_flag("CAH_NO_MULTI_MIXED") || env_flag("CAH_NO_MULTI2")) return;
     int min_adapters = 8;
     if (const char* e = getenv("CAH_MULTI_MIXED_MIN")) { const int v = atoi(e); if (v >= 2) min_adapters = v; }
     if (n < min_adapters || n > CAH_MULTI_MAX_PLAN_ADAPTERS) return;
@@ -840,7 +806,7 @@ static void build_multi_mixed(const cah_adapter_desc* descs, int n, cah_plan* pl
     if (n <= CAH_MULTI_MAX_ADAPTERS) {
         if (m2_build_mixed(ads, ml.thr_last, k_of.data(), ml.min_overlap, ref, mp.m2, &why) && mp.m2.hdr.mixed) {
             fill_multi_tabs(plan, n, mp);
-            mp.mixed = true;
+            mp.form = M_MIXED;
             mp.longest = longest;
             return;
         }
@@ -852,11 +818,11 @@ static void build_multi_mixed(const cah_adapter_desc* descs, int n, cah_plan* pl
 
 static void build_multi(const cah_adapter_desc* descs, int n, cah_plan* plan) {
     MultiPlan& mp = plan->multi;
-    const char* off = getenv("CAH_NO_MULTI");
-    if (off && *off && *off != '0') return;
+    if (env_flag("CAH_NO_MULTI")) return;
+    mp.one_length = true;
+    for (int a = 1; a < n; a++) mp.one_length = mp.one_length && plan->matchers[(size_t)a].m == plan->matchers[0].m;
     // adapters that differ in shape by their LENGTH: the mixed form, or the per-adapter loop
-    for (int a = 1; a < n; a++)
-        if (plan->matchers[(size_t)a].m != plan->matchers[0].m) { build_multi_mixed(descs, n, plan); return; }
+    if (!mp.one_length) { build_multi_mixed(descs, n, plan); return; }
     // below ~8 adapters one lean prefilter pass per adapter is faster than the fused pass (measured on C5:
     // 2 adapters, 2 x 9.9 ms against 75 ms per 125 M reads); CAH_MULTI_MIN overrides the threshold
     int min_adapters = 8;
@@ -866,7 +832,7 @@ static void build_multi(const cah_adapter_desc* descs, int n, cah_plan* plan) {
         // more adapters of one length than a table holds: groups of tables (up to CAH_MULTI_MAX_PLAN_ADAPTERS), no fused form
         int longest = 0;
         std::vector<int> k_of;
-        if (n > CAH_MULTI_MAX_PLAN_ADAPTERS || env_flag_early("CAH_NO_MULTI2") || !multi_stream_eligible(descs, n, plan, longest, k_of)) return;
+        if (n > CAH_MULTI_MAX_PLAN_ADAPTERS || env_flag("CAH_NO_MULTI2") || !multi_stream_eligible(descs, n, plan, longest, k_of)) return;
         std::vector<std::string> ads;
         std::vector<std::vector<M2RefKmer>> ref;
         m2_ref_sets(descs, n, ads, ref);
@@ -952,10 +918,10 @@ static void build_multi(const cah_adapter_desc* descs, int n, cah_plan* plan) {
     h.n_entries = (uint32_t)mp.entries.size();
     fill_multi_tabs(plan, n, mp);
     h.ok = 1;
+    mp.form = M_ONE_SHAPE;
     // the streaming form (multi2.h): the same plan as tables of REF + WIDE k-mers of up to ten characters.
     // CAH_NO_MULTI2=1 keeps the older kernels (A/B, parity tests)
-    const char* off2 = getenv("CAH_NO_MULTI2");
-    if (!(off2 && *off2 && *off2 != '0')) {
+    if (!env_flag("CAH_NO_MULTI2")) {
         std::vector<std::string> ads;
         std::vector<std::vector<M2RefKmer>> ref;
         m2_ref_sets(descs, n, ads, ref);
@@ -1110,18 +1076,9 @@ int cah_plan_multi_groups(const cah_plan* plan, int32_t* out) {
 
 int cah_plan_multi_kind(const cah_plan* plan, int32_t read_len, int32_t* out) {
     if (!plan || !out) return fail(CAH_EINVAL, "plan or out is NULL");
-    const MultiPlan& mp = plan->multi;
-    if (mp.mixed) {                                          // (no fused form behind the mixed one, nor behind groups of tables)
-        bool len_ok = mp.n_tables() > 0;
-        for (int g = 0; g < mp.n_tables(); g++) len_ok = len_ok && multi2_read_len_ok(mp.tables(g).hdr, read_len);
-        bool off = env_flag_early("CAH_NO_MULTI2") || env_flag_early("CAH_NO_MULTI");
-        if (!mp.groups.empty()) off = off || env_flag_early("CAH_NO_MULTI_GROUPS");
-        if (!mp.groups_one_length) off = off || env_flag_early("CAH_NO_MULTI_MIXED");
-        *out = (len_ok && !off) ? CAH_MULTI_STREAM : CAH_MULTI_SEQUENTIAL;
-        return CAH_OK;
-    }
-    *out = !mp.hdr.ok ? CAH_MULTI_SEQUENTIAL
-                      : ((mp.m2.hdr.ok && multi2_read_len_ok(mp.m2.hdr, read_len) && !env_flag_early("CAH_NO_MULTI2")) ? CAH_MULTI_STREAM : CAH_MULTI_FUSED);
+    MultiBatch b;                                            // a uniform batch of this length in a workspace that fits
+    b.ul.len = read_len; b.ws_fits = true;
+    *out = multi_route(plan->multi, b, multi_switches()).path;
     return CAH_OK;
 }
 
@@ -1226,8 +1183,8 @@ static const size_t WS_M2_ERR = 968 / sizeof(unsigned long long);     // multi2'
 static const size_t WS_RETRYCOUNT = 576 / sizeof(unsigned long long), WS_RETRYWORK = 704 / sizeof(unsigned long long);
 static int64_t ws_retry_cap(int64_t n_reads) { return n_reads / 8 + 1024; }
 
-static size_t ws_queue_bytes(int64_t n_reads) { return (sizeof(int32_t) * (size_t)n_reads + 255) & ~(size_t)255; }
-static size_t ws_keys_bytes(int64_t n_reads) { return ((size_t)n_reads + 255) & ~(size_t)255; }
+static size_t ws_queue_bytes(int64_t n_reads) { return ws_align256(sizeof(int32_t) * (size_t)n_reads); }
+static size_t ws_keys_bytes(int64_t n_reads) { return ws_align256((size_t)n_reads); }
 
 size_t cah_workspace_bytes(int64_t n_reads) {
     if (n_reads < 0) n_reads = 0;
@@ -1235,27 +1192,12 @@ size_t cah_workspace_bytes(int64_t n_reads) {
            ws_queue_bytes(ws_retry_cap(n_reads)) + ws_keys_bytes(ws_retry_cap(n_reads)) + 256;
 }
 
-// ---- extra scratch of the fused multi-adapter path: [best key 8n] [pairs 8*cap] [DP list 4*cap] [windows 8*cap]
-// cap = pairs one chunk of reads can produce in the worst case (every adapter on every read), bounded by
-// CAH_MULTI_PAIR_CAP (default 1 G pairs = 20 GB of scratch on a 288 GB device: every chunk costs the cell DP a launch
-// whose duration is that of its slowest wave, ~0.45 ms, however few pairs it has -- at 256 M pairs a 100 M-read batch
-// of 96 adapters paid that 36 times, 16 of its 114 ms); larger batches are processed in chunks of
-// cap / n_adapters reads.
-// The streaming form's pool (multi2.h: pages of CAH_M2_PAGE pairs, one class each).  A closed page may lack up to 63
-// pairs; every wave of a block holds one open page per class; a block has at most three tiles in flight (its waves may
-// straddle two, the third is drawn ahead).
-static int64_t m2_pages_per_tile(int64_t A) { return (1024 * A + (CAH_M2_PAGE - 64)) / (CAH_M2_PAGE - 63); }   // (multi2.hip: M2_TILE)
-static int64_t m2_block_reserve(int64_t A) { return 3 * m2_pages_per_tile(A) + 16 * CAH_M2_PAIR_CLASSES; }
-static int64_t m2_pages_worst(int64_t A, int64_t n_reads) {
-    const int64_t tiles = (n_reads + 1023) / 1024;
-    return tiles * m2_pages_per_tile(A) + std::min<int64_t>(std::max<int64_t>(tiles, 1), 512) * 16 * CAH_M2_PAIR_CLASSES + 2;
-}
-// pairs the scratch has room for: what the batch can produce in the worst case (every adapter on every read), bounded
-// by CAH_MULTI_PAIR_CAP (default: default_pair_limit() below -- 2 G pairs = 40 GB on an empty 288 GB device).  The fused form handles larger
-// batches in chunks of cap / n_adapters reads; the streaming form in ROUNDS that end when the pool runs low (a typical
-// batch of 100 M reads x 96 adapters has 0.45 G pairs and takes one).
+// ---- extra scratch of the multi-adapter path (multi_route.h: MultiScratch, and the arithmetic of the streaming form's
+// page pool).  cap = pairs one chunk of reads can produce in the worst case (every adapter on every read), bounded by
+// CAH_MULTI_PAIR_CAP: every chunk costs the cell DP a launch whose duration is that of its slowest wave, ~0.45 ms, however
+// few pairs it has -- at 256 M pairs a 100 M-read batch of 96 adapters paid that 36 times, 16 of its 114 ms.
 // The default bound follows the device: a quarter of the HBM that is FREE when a device's first multi-adapter workspace is
-// sized (20 bytes of scratch per pair), at most 2 G pairs, at least 64 M; asked once per device and kept, because the
+// sized (MultiScratch::pair_bytes of scratch per pair), at most 2 G pairs, at least 64 M; asked once per device and kept, because the
 // sizing call (cah_plan_workspace_bytes) and every later match call must agree on the layout.  Without a usable device
 // (the CPU-side tests ask for sizes too) it is 2 G pairs.
 static int64_t default_pair_limit() {
@@ -1268,7 +1210,7 @@ static int64_t default_pair_limit() {
         size_t free_b = 0, total_b = 0;
         int64_t limit = 2048ll << 20;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-            limit = std::min<int64_t>(limit, std::max<int64_t>(64ll << 20, (int64_t)(free_b / 4 / 20)));
+            limit = std::min<int64_t>(limit, std::max<int64_t>(64ll << 20, (int64_t)(free_b / 4 / MultiScratch::pair_bytes)));
         else (void)hipGetLastError();
         per_device[dev] = limit;
     }
@@ -1278,20 +1220,9 @@ static int64_t multi_pair_cap(const cah_plan* plan, int64_t n_reads) {
     int64_t limit = 0;
     if (const char* e = getenv("CAH_MULTI_PAIR_CAP")) { const long long v = atoll(e); if (v > 0) limit = v; }
     if (limit <= 0) limit = default_pair_limit();
-    // (the cell DP's work list holds pair indices as int32: the pool never has 2^31 pairs or more, whatever the knob says)
-    limit = std::min<int64_t>(limit, ((int64_t)1 << 31) - 4 * CAH_M2_PAGE);
     // (groups of tables share the pool one after the other: the LARGEST group sizes it, not the plan's adapter count)
-    const int64_t A = (int64_t)plan->multi.largest_group((int)plan->matchers.size());
-    if (limit < A) limit = A;
-    const int64_t fused = std::min(n_reads * A, limit);
-    if (plan->multi.n_tables() == 0) return fused;          // (no streaming form for this plan: no page pool, no floor)
-    // (one block of the streaming prefilter must always be able to run)
-    const int64_t floor_pages = 2 * m2_block_reserve(A) + 2 * m2_pages_per_tile(A);
-    const int64_t pages = std::min(m2_pages_worst(A, n_reads), std::max(limit / CAH_M2_PAGE, floor_pages));
-    // (a page header word per page lives behind the pages, inside the pair area)
-    return std::max(fused, pages * CAH_M2_PAGE + pages / 2 + 2);
+    return m2_pair_cap(limit, plan->multi.largest_group((int)plan->matchers.size()), n_reads, plan->multi.n_tables() > 0);
 }
-static size_t ws_key_bytes(int64_t n_reads) { return (sizeof(unsigned long long) * (size_t)n_reads + 255) & ~(size_t)255; }
 
 // column scratch of k_dp_long: 3 int32 per row and lane, for as many lanes as the kernel is launched with
 // (sized for a 256-CU device; fewer lanes are launched if the caller's workspace is smaller)
@@ -1302,8 +1233,7 @@ static size_t long_scratch_bytes(const cah_plan* plan, int64_t lanes) {
 size_t cah_plan_workspace_bytes(const cah_plan* plan, int64_t n_reads) {
     if (n_reads < 0) n_reads = 0;
     size_t need = cah_workspace_bytes(n_reads);
-    if (plan && (plan->multi.hdr.ok || plan->multi.mixed))
-        need += ws_key_bytes(n_reads) + (size_t)multi_pair_cap(plan, n_reads) * 20 + 2 * ws_keys_bytes(n_reads) + 256;
+    if (plan && plan->multi.form != M_NONE) need += MultiScratch::bytes(multi_pair_cap(plan, n_reads), n_reads);
     if (plan && plan->max_long_m > 0) need += long_scratch_bytes(plan, long_scratch_lanes(n_reads, 256)) + 256;
     return need;
 }
@@ -1360,7 +1290,7 @@ struct CallHints {
 // Aligner of an anchored adapter (Where.PREFIX = QUERY_STOP, Where.SUFFIX = QUERY_START) whose error threshold at
 // full length is 0: see k_anchored_exact.  CAH_NO_ANCHORED_EXACT=1 keeps the cell DP (A/B, parity tests).
 static bool anchored_exact_ok(const CahMatcher& mt) {
-    static const bool off = [] { const char* e = getenv("CAH_NO_ANCHORED_EXACT"); return e && *e && *e != '0'; }();
+    static const bool off = env_flag("CAH_NO_ANCHORED_EXACT");
     return !off && !mt.long_dp && (mt.flags == 8 || mt.flags == 2) && mt.m >= 1 && mt.m <= CAH_MAX_M &&
            mt.effective_length >= 0 && mt.effective_length <= CAH_MAX_M && mt.thr[mt.effective_length] == 0 &&
            mt.min_overlap <= mt.m;
@@ -1373,7 +1303,7 @@ static bool runs_filter(const CahMatcher& mt) {
 
 // CAH_SCAN_WORD64=1: the cost scan always uses the 64-bit form of the column (A/B measurements, parity tests)
 static int scan_word_kind(int m) {
-    static const bool force64 = [] { const char* e = getenv("CAH_SCAN_WORD64"); return e && *e && *e != '0'; }();
+    static const bool force64 = env_flag("CAH_SCAN_WORD64");
     return force64 ? 0 : bs_kind_of(m);
 }
 
@@ -1397,13 +1327,6 @@ static int64_t scan_retry_cap(int64_t cap) {
 // column window); everything else runs the cell kernel directly.
 // equally long reads the host vouches for (cah_match_batch_uniform): read r = d_seqs[first + r * len ..); len == 0: the
 // packed layout (offsets / lens)
-static bool env_flag(const char* name) { const char* e = getenv(name); return e && *e && *e != '0'; }
-
-// suffix: (first, len) describe a PARENT batch of equally long reads and d_offsets / d_lens views that end where
-// its reads end (cah_match_batch_suffix_views): only the streaming prefilter makes use of that, every other kernel
-// sees plain views.
-// inner (with suffix): the views may end before the parent's reads do (cah_match_batch_views)
-struct UniformLayout { int64_t first = 0; int32_t len = 0; bool suffix = false; bool inner = false; bool general = false; };
 // cah_linked_match_batch_uniform, fused form: the streaming prefilter of the back adapter decides the views itself
 // (kernels.h: FilterArgs::front) and writes the front stage's outputs and the views
 struct FrontFuse {
@@ -1649,212 +1572,173 @@ int cah_last_multi_path(void) { return t_last_multi_path; }
 static thread_local int t_deferred_errors = 0;
 int cah_set_deferred_errors(int on) { const int old = t_deferred_errors; t_deferred_errors = on ? 1 : 0; return old; }
 
-// Does the streaming form (multi2.hip) take this batch of this plan?  Equally long reads (no lengths array), or views /
-// frames of such a length (ul.inner: d_offsets / d_lens are the views' starts and lengths), of a length the plan's tables
-// allow.  ONE predicate for match_batch_multi_once, which streams or falls to the fused kernels by it, and for
-// match_batch_impl, which sends a MIXED plan -- no fused kernels behind it -- to the per-adapter loop where it is false.
-static bool multi_streams(const MultiPlan& mp, const UniformLayout& ul, const int64_t* d_offsets, const int32_t* d_lens) {
-    const bool views = ul.inner && d_lens != nullptr && d_offsets != nullptr;
-    if (mp.n_tables() == 0 || ul.len <= 0 || !(!d_lens || (views && !env_flag("CAH_NO_MULTI2_VIEWS"))) || env_flag("CAH_NO_MULTI2")) return false;
-    if (!mp.groups.empty() && env_flag("CAH_NO_MULTI_GROUPS")) return false;
-    for (int g = 0; g < mp.n_tables(); g++)                  // (groups of tables: every group must take the length)
-        if (!multi2_read_len_ok(mp.tables(g).hdr, ul.len)) return false;
-    return true;
+static thread_local bool t_m2_waited_in_vain = false;     // the last failure of match_batch_multi_once was err bit 1 alone
+
+// what one call of the multi-adapter path works on; ul: the layout its route gives the path (multi_route.h)
+struct MultiCall {
+    const cah_plan* plan; const PlanDeviceCopy* pd;
+    const uint8_t* d_seqs; const int64_t* d_offsets; const int32_t* d_lens; int64_t n_reads;
+    int32_t* d_out6; int32_t* d_best_adapter; uint8_t* d_status;
+    unsigned long long* counters; hipStream_t s; UniformLayout ul;
+    int64_t cap;                                             // multi_pair_cap: the pairs the scratch has room for
+    MultiScratch sc;
+};
+
+// libcutadapt_hip_dev.so only (cutadapt_amd/build.py: build_dev_library; tests/test_gpu_multi2.py): takes the pool's
+// gate away to provoke its overflow.  The product library does not hold this switch.
+static bool m2_ungated() {
+#ifdef CAH_DEV_KNOBS
+    return env_flag("CAH_TEST_M2_UNGATED");
+#else
+    return false;
+#endif
 }
 
-static thread_local bool t_m2_waited_in_vain = false;     // the last failure of match_batch_multi_once was err bit 1 alone
-static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd, const uint8_t* d_seqs,
-                                  const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads, int32_t* d_out6,
-                                  int32_t* d_best_adapter, uint8_t* d_status, const Workspace& ws, char* extra,
-                                  hipStream_t s, const UniformLayout ul);
-// (a wave that gave up waiting for its tile -- err bit 1: nothing is wrong with the batch, the device was busy with
-// something else for seconds -- is no reason to fail the call: the batch is matched once more from the start)
-static int match_batch_multi(const cah_plan* plan, const PlanDeviceCopy* pd, const uint8_t* d_seqs,
-                             const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads, int32_t* d_out6,
-                             int32_t* d_best_adapter, uint8_t* d_status, const Workspace& ws, char* extra,
-                             hipStream_t s, const UniformLayout ul = UniformLayout()) {
-    t_m2_waited_in_vain = false;
-    int rc = match_batch_multi_once(plan, pd, d_seqs, d_offsets, d_lens, n_reads, d_out6, d_best_adapter, d_status, ws, extra, s, ul);
-    if (rc == CAH_EINTERNAL && t_m2_waited_in_vain) {
-        t_m2_waited_in_vain = false;
-        rc = match_batch_multi_once(plan, pd, d_seqs, d_offsets, d_lens, n_reads, d_out6, d_best_adapter, d_status, ws, extra, s, ul);
+// The streaming form (multi2.hip), ONE group of tables on ONE block of reads [lo, lo + cnt): k_multi_stream emits the pairs
+// in pages of one class each (the suffix compare of the error-free rows happens there), k_multi_scan scans them page by
+// page, the cell DP takes what the scan left -- in as many rounds as the pool asks for (m2_pool_shape).
+static int run_stream_group(const MultiCall& c, int g, int64_t lo, int64_t cnt, bool deferred) {
+    const MultiPlan& mp = c.plan->multi;
+    const PlanDeviceCopy* pd = c.pd;
+    const UniformLayout& ul = c.ul;
+    hipStream_t s = c.s;
+    unsigned long long* counters = c.counters;
+    const bool views = ul.inner && c.d_lens != nullptr && c.d_offsets != nullptr;    // views inside the reads of a uniform batch
+    // the pool: pages of CAH_M2_PAGE pairs + one header word each, inside the pair area
+    const int64_t max_pages = m2_pool_pages(c.cap), open_pages = 16 * CAH_M2_PAIR_CLASSES;
+    uint32_t* d_page_hdr = (uint32_t*)(c.sc.pairs + max_pages * CAH_M2_PAGE);
+    const int64_t TILE = multi2_tile_reads(), n_tiles = (cnt + TILE - 1) / TILE;
+    const M2Tables& tb = mp.tables(g);
+    const M2DeviceTables& dt = pd->d_m2[(size_t)g];
+    const int base = mp.group_base(g);
+    const int64_t Ag = mp.group_count(g, (int)c.plan->matchers.size()), per_tile = m2_pages_per_tile(Ag);
+    const bool g_mixed = tb.hdr.mixed != 0;
+    // (a group of different lengths: every pair with its own adapter's length; word form, ROWS and thr_last from the
+    // group's longest -- the explicit-row forms of 33 / 34 characters have no pad rows for a shorter adapter: the 64-bit
+    // form serves.  A group of one length takes the one-shape kernels with its first adapter's shape)
+    const CahMatcher& mlong = c.plan->matchers[(size_t)(base + mp.group_longest(g))];
+    const M2PoolShape sh = m2_pool_shape(Ag, cnt, max_pages, pd->n_cus, m2_ungated());
+    // (a later group of the block keeps the error word of the groups before it: WS_M2_ERR lies behind what is zeroed)
+    HIP_TRY(hipMemsetAsync(counters, 0, g == 0 ? WS_HEADER : WS_M2_ERR * sizeof(unsigned long long), s));
+    for (int64_t round = 0;; round++) {
+        if (round >= sh.rounds && deferred) break;
+        if (round >= sh.rounds) {
+            // The planned rounds are through.  Never trust the arithmetic above silently: the device says how many
+            // tiles were drawn and whether a kernel ran out of pages or waited in vain (kernels.h: Multi2Args::err).
+            unsigned long long st[2] = {0ull, 0ull};                // {tiles drawn, error bits}
+            HIP_TRY(hipMemcpyAsync(st, counters + WS_M2_TILE, sizeof(st), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            t_m2_waited_in_vain = st[1] == 2ull;
+            if (st[1])
+                return fail(CAH_EINTERNAL, "multi-adapter path: %s (pool of %lld pages, %lld adapters, %lld reads): results discarded",
+                            (st[1] & 1ull) ? "the page pool ran out" : "a wave waited in vain for its tile",
+                            (long long)max_pages, (long long)Ag, (long long)cnt);
+            if ((int64_t)st[0] >= n_tiles) break;
+            // tiles are left (the worst-case round count was too small): go on, a round at a time
+            if (round >= sh.rounds + 4 * n_tiles)
+                return fail(CAH_EINTERNAL, "multi-adapter path: %lld of %lld tiles left after %lld rounds",
+                            (long long)(n_tiles - (int64_t)st[0]), (long long)n_tiles, (long long)round);
+        }
+        if (round) HIP_TRY(hipMemsetAsync(counters, 0, WS_M2_TILE * sizeof(unsigned long long), s));
+        // (the profile counts the batch's reads once: a further round, or a further group, is the same pass over them)
+        const int64_t units = (round || g) ? -1 : cnt;
+        {
+            Multi2Args f;
+            f.uniform_first = ul.first; f.uniform_len = ul.len;
+            f.win_hi = tb.hdr.win_dist[M2_HI]; f.win_lo = tb.hdr.win_dist[M2_LO];
+            f.hdr = dt.d_m2hdr; f.dir = dt.d_m2dir; f.entries = dt.d_m2entries; f.bitmap = dt.d_m2bitmap;
+            f.prefix = dt.d_m2prefix;
+            f.seqs = c.d_seqs; f.first_read = lo; f.n_reads = cnt; f.status = c.d_status; f.best_key = c.sc.best_key;
+            f.pairs = c.sc.pairs; f.page_hdr = d_page_hdr; f.page_counter = counters + WS_QCOUNT; f.max_pages = max_pages;
+            f.tile_counter = counters + WS_M2_TILE; f.n_tiles = n_tiles; f.gate_pages = sh.gate;
+            f.err = counters + WS_M2_ERR;
+            f.wmeta = c.sc.wmeta;
+            f.adapter_base = base;
+            if (views) { f.view_starts = c.d_offsets; f.view_lens = c.d_lens; f.view_general = ul.general ? 1 : 0; }
+            ProfScope ps(s, CAH_PROF_FILTER, units);
+            HIP_TRY(launch_multi_stream(f, tb.hdr, (int)sh.grid, s));
+        }
+        {
+            Multi2ScanArgs sa;
+            sa.uniform_first = ul.first; sa.uniform_len = ul.len;
+            sa.kind = scan_word_kind(mlong.m);
+            if (g_mixed) { sa.mixed = 1; sa.longest = mp.group_longest(g); sa.kind = scan_word_kind(mlong.m) == 1 ? 1 : 0; }
+            sa.rows_lo = tb.hdr.rows_lo;
+            sa.matcher = pd->d_matchers + base; sa.tab = pd->d_mscan + (size_t)base * CAH_MULTI_TAB_STRIDE; sa.n_adapters = (int32_t)Ag;
+            sa.seqs = c.d_seqs; sa.pairs = c.sc.pairs; sa.page_hdr = d_page_hdr;
+            sa.page_counter = counters + WS_QCOUNT; sa.max_pages = max_pages; sa.err = counters + WS_M2_ERR;
+            sa.work_counter = counters + WS_SCANWORK; sa.best_key = c.sc.best_key;
+            sa.dp_queue = c.sc.dpq; sa.dp_win = c.sc.win;
+            sa.dp_count_front = counters + WS_DPFRONT; sa.dp_count_back = counters + WS_DPBACK; sa.dp_cap = c.cap;
+            sa.wmeta = c.sc.wmeta; sa.prefix = dt.d_m2prefix; sa.lmax0 = tb.hdr.lmax0;
+            sa.adapter_base = base;
+            if (views) { sa.view_starts = c.d_offsets; sa.view_lens = c.d_lens; sa.view_general = ul.general ? 1 : 0; }
+            // (how many pages there are is known on the device only: the blocks draw pages until none is left)
+            ProfScope ps(s, CAH_PROF_SCAN, units);
+            HIP_TRY(launch_multi_scan(sa, std::min(max_pages, n_tiles * per_tile + sh.grid * open_pages), pd->n_cus, s));
+        }
+        {
+            // the cell DP over the pairs the scan left (the launch returns at once when there are none)
+            DpArgs a;
+            a.uniform_first = ul.first; a.uniform_len = views ? 0 : ul.len;     // (views: the cell DP reads starts + lengths)
+            a.matcher = pd->d_matchers + base;
+            a.seqs = c.d_seqs; a.offsets = c.d_offsets; a.lens = c.d_lens; a.n_reads = cnt * Ag;
+            a.max_read_len = CAH_MAX_READ_LEN;
+            a.queue_keys = nullptr;
+            a.out6 = c.d_out6; a.status = c.d_status; a.best_adapter = c.d_best_adapter;
+            a.adapter_index = 0; a.merge_best = 1;
+            a.pairs = c.sc.pairs; a.tab = pd->d_mrow + (size_t)base * CAH_MULTI_TAB_STRIDE; a.n_adapters = (int32_t)Ag; a.best_key = c.sc.best_key;
+            a.queue = c.sc.dpq; a.queue_count = counters + WS_DPFRONT; a.queue_count_back = counters + WS_DPBACK;
+            a.win = c.sc.win; a.queue_cap = c.cap; a.work_counter = counters + WS_DPWORK;
+            a.m2_hdr = dt.d_m2hdr; a.m2_ref_begin = dt.d_m2refbegin; a.m2_ref_list = dt.d_m2reflist;
+            a.adapter_base = base;
+            ProfScope ps(s, CAH_PROF_DP, units);
+            HIP_TRY(launch_dp(a, mlong.m, true, true, std::min(c.cap, cnt * Ag), pd->n_cus, s, g_mixed));
+        }
     }
-    return rc;
+    return CAH_OK;
 }
-static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd, const uint8_t* d_seqs,
-                                  const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads, int32_t* d_out6,
-                                  int32_t* d_best_adapter, uint8_t* d_status, const Workspace& ws, char* extra,
-                                  hipStream_t s, const UniformLayout ul) {
-    const MultiPlan& mp = plan->multi;
-    const int64_t A = (int64_t)plan->matchers.size();
-    const int64_t cap = multi_pair_cap(plan, n_reads);
+
+// Groups of tables (MultiPlan::groups) go through the pool one after the other: every group's kernels run to their end
+// before the next group's start (one stream), and cap was sized by the largest group (multi_pair_cap).
+static int run_multi_stream(const MultiCall& c) {
+    const MultiPlan& mp = c.plan->multi;
+    // (pairs carry the read's index in 32 bits, the prefilter counts reads in an int)
+    const int64_t BLOCK = (int64_t)1 << 30;
+    // (the deferred form: nothing for the host to decide in ANY group, known before the first group runs)
+    const bool deferred = t_deferred_errors && c.n_reads <= BLOCK &&
+                          m2_one_launch_for_all(mp, (int)c.plan->matchers.size(), c.n_reads, m2_pool_pages(c.cap), c.pd->n_cus, m2_ungated());
+    for (int64_t lo = 0; lo < c.n_reads; lo += BLOCK)
+        for (int g = 0; g < mp.n_tables(); g++) {
+            const int rc = run_stream_group(c, g, lo, std::min(BLOCK, c.n_reads - lo), deferred);
+            if (rc) return rc;
+        }
+    ProfScope ps(c.s, CAH_PROF_MERGE, c.n_reads);
+    HIP_TRY(launch_multi_decode(c.sc.best_key, c.n_reads, c.d_out6, c.d_status, c.d_best_adapter, c.pd->n_cus, c.s,
+                                deferred ? c.counters + WS_M2_ERR : nullptr));
+    return CAH_OK;
+}
+
+// The older fused kernels (multi.hip; one-shape plans), in chunks of cap / n_adapters reads
+static int run_multi_fused(const MultiCall& c) {
+    const MultiPlan& mp = c.plan->multi;
+    const PlanDeviceCopy* pd = c.pd;
+    const UniformLayout& ulo = c.ul;
+    hipStream_t s = c.s;
+    unsigned long long* counters = c.counters;
+    const int64_t A = (int64_t)c.plan->matchers.size(), cap = c.cap;
     const int64_t chunk = std::max<int64_t>(1, cap / A);
-    unsigned long long* d_best_key = (unsigned long long*)extra;     extra += ws_key_bytes(n_reads);
-    uint64_t* d_pairs = (uint64_t*)extra;                            extra += (size_t)cap * 8;
-    int32_t* d_dpq = (int32_t*)extra;                                extra += (size_t)cap * 4;
-    int32_t* d_win = (int32_t*)extra;                                extra += (size_t)cap * 8;
-    uint16_t* d_wmeta = (uint16_t*)extra;                            // (streaming form: a 16-bit word per read, multi2.h)
-    unsigned long long* counters = ws.counters;
-    const CahMatcher& m0 = plan->matchers[0];
-    HIP_TRY(hipMemsetAsync(d_best_key, 0, sizeof(unsigned long long) * (size_t)n_reads, s));
-    // Equally long short reads take the streaming form (multi2.hip): k_multi_stream emits the pairs in pages of one
-    // class each (the suffix compare of the error-free rows happens there), k_multi_scan scans them page by page.
-    t_last_multi_path = CAH_MULTI_FUSED;
-    const bool views = ul.inner && d_lens != nullptr && d_offsets != nullptr;    // views inside the reads of a uniform batch
-    if (multi_streams(mp, ul, d_offsets, d_lens)) {
-        t_last_multi_path = CAH_MULTI_STREAM;
-        // the pool: pages of CAH_M2_PAGE pairs + one header word each, inside the pair area.  Groups of tables (MultiPlan::
-        // groups) go through it one after the other: every group's kernels run to their end before the next group's start
-        // (one stream), and cap was sized by the largest group (multi_pair_cap)
-        const int64_t max_pages = ((int64_t)cap * 8) / (CAH_M2_PAGE * 8 + 4);
-        uint32_t* d_page_hdr = (uint32_t*)(d_pairs + max_pages * CAH_M2_PAGE);
-        const int64_t TILE = multi2_tile_reads(), open_pages = 16 * CAH_M2_PAIR_CLASSES;
-        const int G = mp.n_tables();
-        // (pairs carry the read's index in 32 bits, the prefilter counts reads in an int)
-        const int64_t BLOCK = (int64_t)1 << 30;
-        // the gate and the rounds of a group on a block of cnt reads: pure arithmetic, asked twice -- the deferred form
-        // holds only if EVERY group qualifies, which must be known before the first group runs
-        struct Shape { int64_t grid, gate, rounds; bool ungated; };
-        auto shape_of = [&](int g, int64_t cnt) {
-            const int64_t Ag = mp.group_count(g, (int)A), per_tile = m2_pages_per_tile(Ag);
-            const int64_t n_tiles = (cnt + TILE - 1) / TILE;
-            Shape sh{std::min<int64_t>(n_tiles, pd->n_cus), max_pages, 1, false};
-            if (n_tiles * per_tile + sh.grid * open_pages > max_pages) {
-                // the batch might not fit the pool: blocks stop drawing tiles once what is in flight could fill it, and
-                // the rounds go on until the tiles are done -- `rounds` is the count for the worst case (every adapter on
-                // every read); a round that finds no tile left costs four empty launches
-                sh.grid = std::max<int64_t>(1, std::min(sh.grid, (max_pages / 2) / m2_block_reserve(Ag)));
-                sh.gate = max_pages - sh.grid * m2_block_reserve(Ag);
-                const int64_t sure = std::max<int64_t>(1, (sh.gate - sh.grid * open_pages) / per_tile);
-                sh.rounds = (n_tiles + sure - 1) / sure;
-            }
-#ifdef CAH_DEV_KNOBS
-            // libcutadapt_hip_dev.so only (cutadapt_amd/build.py: build_dev_library; tests/test_gpu_multi2.py): takes the
-            // gate away to provoke the pool's overflow.  The product library does not hold this switch.
-            if (env_flag("CAH_TEST_M2_UNGATED")) { sh.gate = (int64_t)1 << 60; sh.rounds = 1; sh.ungated = true; }
-#endif
-            return sh;
-        };
-        // (the pool holds the worst case of the whole batch, one launch draws every tile: nothing for the host to decide)
-        bool deferred = t_deferred_errors && n_reads <= BLOCK;
-        for (int g = 0; g < G && deferred; g++) {
-            const Shape sh = shape_of(g, n_reads);
-            deferred = sh.rounds == 1 && (sh.gate == max_pages || sh.ungated);
-        }
-        for (int64_t lo = 0; lo < n_reads; lo += BLOCK) {
-            const int64_t cnt = std::min(BLOCK, n_reads - lo);
-            const int64_t n_tiles = (cnt + TILE - 1) / TILE;
-          for (int g = 0; g < G; g++) {
-            const M2Tables& tb = mp.tables(g);
-            const M2DeviceTables& dt = pd->d_m2[(size_t)g];
-            const int base = mp.group_base(g);
-            const int64_t Ag = mp.group_count(g, (int)A), per_tile = m2_pages_per_tile(Ag);
-            const bool g_mixed = tb.hdr.mixed != 0;
-            // (a group of different lengths: every pair with its own adapter's length; word form, ROWS and thr_last from the
-            // group's longest -- the explicit-row forms of 33 / 34 characters have no pad rows for a shorter adapter: the 64-bit
-            // form serves.  A group of one length takes the one-shape kernels with its first adapter's shape)
-            const CahMatcher& mlong = plan->matchers[(size_t)(base + mp.group_longest(g))];
-            const Shape sh = shape_of(g, cnt);
-            const int64_t grid = sh.grid, gate = sh.gate, rounds = sh.rounds;
-            // (a later group of the block keeps the error word of the groups before it: WS_M2_ERR lies behind what is zeroed)
-            HIP_TRY(hipMemsetAsync(counters, 0, g == 0 ? WS_HEADER : WS_M2_ERR * sizeof(unsigned long long), s));
-          for (int64_t round = 0;; round++) {
-            if (round >= rounds && deferred) break;
-            if (round >= rounds) {
-                // The planned rounds are through.  Never trust the arithmetic above silently: the device says how many
-                // tiles were drawn and whether a kernel ran out of pages or waited in vain (kernels.h: Multi2Args::err).
-                unsigned long long st[2] = {0ull, 0ull};                // {tiles drawn, error bits}
-                HIP_TRY(hipMemcpyAsync(st, counters + WS_M2_TILE, sizeof(st), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipStreamSynchronize(s));
-                t_m2_waited_in_vain = st[1] == 2ull;
-                if (st[1])
-                    return fail(CAH_EINTERNAL, "multi-adapter path: %s (pool of %lld pages, %lld adapters, %lld reads): results discarded",
-                                (st[1] & 1ull) ? "the page pool ran out" : "a wave waited in vain for its tile",
-                                (long long)max_pages, (long long)Ag, (long long)cnt);
-                if ((int64_t)st[0] >= n_tiles) break;
-                // tiles are left (the worst-case round count was too small): go on, a round at a time
-                if (round >= rounds + 4 * n_tiles)
-                    return fail(CAH_EINTERNAL, "multi-adapter path: %lld of %lld tiles left after %lld rounds",
-                                (long long)(n_tiles - (int64_t)st[0]), (long long)n_tiles, (long long)round);
-            }
-            if (round) HIP_TRY(hipMemsetAsync(counters, 0, WS_M2_TILE * sizeof(unsigned long long), s));
-            // (the profile counts the batch's reads once: a further round, or a further group, is the same pass over them)
-            const int64_t units = (round || g) ? -1 : cnt;
-            {
-                Multi2Args f;
-                f.uniform_first = ul.first; f.uniform_len = ul.len;
-                f.win_hi = tb.hdr.win_dist[M2_HI]; f.win_lo = tb.hdr.win_dist[M2_LO];
-                f.hdr = dt.d_m2hdr; f.dir = dt.d_m2dir; f.entries = dt.d_m2entries; f.bitmap = dt.d_m2bitmap;
-                f.prefix = dt.d_m2prefix;
-                f.seqs = d_seqs; f.first_read = lo; f.n_reads = cnt; f.status = d_status; f.best_key = d_best_key;
-                f.pairs = d_pairs; f.page_hdr = d_page_hdr; f.page_counter = counters + WS_QCOUNT; f.max_pages = max_pages;
-                f.tile_counter = counters + WS_M2_TILE; f.n_tiles = n_tiles; f.gate_pages = gate;
-                f.err = counters + WS_M2_ERR;
-                f.wmeta = d_wmeta;
-                f.adapter_base = base;
-                if (views) { f.view_starts = d_offsets; f.view_lens = d_lens; f.view_general = ul.general ? 1 : 0; }
-                ProfScope ps(s, CAH_PROF_FILTER, units);
-                HIP_TRY(launch_multi_stream(f, tb.hdr, (int)grid, s));
-            }
-            {
-                Multi2ScanArgs sa;
-                sa.uniform_first = ul.first; sa.uniform_len = ul.len;
-                sa.kind = scan_word_kind(mlong.m);
-                if (g_mixed) { sa.mixed = 1; sa.longest = mp.group_longest(g); sa.kind = scan_word_kind(mlong.m) == 1 ? 1 : 0; }
-                sa.rows_lo = tb.hdr.rows_lo;
-                sa.matcher = pd->d_matchers + base; sa.tab = pd->d_mscan + (size_t)base * CAH_MULTI_TAB_STRIDE; sa.n_adapters = (int32_t)Ag;
-                sa.seqs = d_seqs; sa.pairs = d_pairs; sa.page_hdr = d_page_hdr;
-                sa.page_counter = counters + WS_QCOUNT; sa.max_pages = max_pages; sa.err = counters + WS_M2_ERR;
-                sa.work_counter = counters + WS_SCANWORK; sa.best_key = d_best_key;
-                sa.dp_queue = d_dpq; sa.dp_win = d_win;
-                sa.dp_count_front = counters + WS_DPFRONT; sa.dp_count_back = counters + WS_DPBACK; sa.dp_cap = cap;
-                sa.wmeta = d_wmeta; sa.prefix = dt.d_m2prefix; sa.lmax0 = tb.hdr.lmax0;
-                sa.adapter_base = base;
-                if (views) { sa.view_starts = d_offsets; sa.view_lens = d_lens; sa.view_general = ul.general ? 1 : 0; }
-                // (how many pages there are is known on the device only: the blocks draw pages until none is left)
-                ProfScope ps(s, CAH_PROF_SCAN, units);
-                HIP_TRY(launch_multi_scan(sa, std::min(max_pages, n_tiles * per_tile + grid * open_pages), pd->n_cus, s));
-            }
-            {
-                // the cell DP over the pairs the scan left (the launch returns at once when there are none)
-                DpArgs a;
-                a.uniform_first = ul.first; a.uniform_len = views ? 0 : ul.len;     // (views: the cell DP reads starts + lengths)
-                a.matcher = pd->d_matchers + base;
-                a.seqs = d_seqs; a.offsets = d_offsets; a.lens = d_lens; a.n_reads = cnt * Ag;
-                a.max_read_len = CAH_MAX_READ_LEN;
-                a.queue_keys = nullptr;
-                a.out6 = d_out6; a.status = d_status; a.best_adapter = d_best_adapter;
-                a.adapter_index = 0; a.merge_best = 1;
-                a.pairs = d_pairs; a.tab = pd->d_mrow + (size_t)base * CAH_MULTI_TAB_STRIDE; a.n_adapters = (int32_t)Ag; a.best_key = d_best_key;
-                a.queue = d_dpq; a.queue_count = counters + WS_DPFRONT; a.queue_count_back = counters + WS_DPBACK;
-                a.win = d_win; a.queue_cap = cap; a.work_counter = counters + WS_DPWORK;
-                a.m2_hdr = dt.d_m2hdr; a.m2_ref_begin = dt.d_m2refbegin; a.m2_ref_list = dt.d_m2reflist;
-                a.adapter_base = base;
-                ProfScope ps(s, CAH_PROF_DP, units);
-                HIP_TRY(launch_dp(a, mlong.m, true, true, std::min(cap, cnt * Ag), pd->n_cus, s, g_mixed));
-            }
-          }
-          }
-        }
-        ProfScope ps(s, CAH_PROF_MERGE, n_reads);
-        HIP_TRY(launch_multi_decode(d_best_key, n_reads, d_out6, d_status, d_best_adapter, pd->n_cus, s,
-                                    deferred ? counters + WS_M2_ERR : nullptr));
-        return CAH_OK;
-    }
-    if (mp.mixed) return fail(CAH_EINTERNAL, "multi-adapter path: a mixed plan has no fused form for this batch");
-    // (the older kernels take views through their starts and lengths alone)
-    const UniformLayout ulo = ul.inner ? UniformLayout() : ul;
-    for (int64_t lo = 0; lo < n_reads; lo += chunk) {
-        const int64_t cnt = std::min(chunk, n_reads - lo);
+    for (int64_t lo = 0; lo < c.n_reads; lo += chunk) {
+        const int64_t cnt = std::min(chunk, c.n_reads - lo);
         HIP_TRY(hipMemsetAsync(counters, 0, WS_HEADER, s));
         {
             MultiFilterArgs f;
             f.uniform_first = ulo.first; f.uniform_len = ulo.len;
             f.hdr = pd->d_mhdr; f.dir = pd->d_mdir; f.entries = pd->d_mentries; f.bitmap = pd->d_mbitmap;
-            f.seqs = d_seqs; f.offsets = d_offsets; f.lens = d_lens;
+            f.seqs = c.d_seqs; f.offsets = c.d_offsets; f.lens = c.d_lens;
             f.first_read = lo; f.n_reads = cnt; f.max_read_len = CAH_MAX_READ_LEN;
-            f.work_counter = counters + 0; f.status = d_status;
-            f.pairs = d_pairs; f.pair_count = counters + WS_QCOUNT; f.pair_cap = cap;
+            f.work_counter = counters + 0; f.status = c.d_status;
+            f.pairs = c.sc.pairs; f.pair_count = counters + WS_QCOUNT; f.pair_cap = cap;
             ProfScope ps(s, CAH_PROF_FILTER, cnt);
             HIP_TRY(launch_multi_filter(f, mp.hdr, pd->n_cus, s));
         }
@@ -1862,20 +1746,20 @@ static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd
             ScanArgs sa;
             sa.uniform_first = ulo.first; sa.uniform_len = ulo.len;
             sa.matcher = pd->d_matchers;
-            sa.seqs = d_seqs; sa.offsets = d_offsets; sa.lens = d_lens; sa.n_reads = cnt * A;
+            sa.seqs = c.d_seqs; sa.offsets = c.d_offsets; sa.lens = c.d_lens; sa.n_reads = cnt * A;
             sa.max_read_len = CAH_MAX_READ_LEN;
             sa.queue = nullptr; sa.queue_count = counters + WS_QCOUNT; sa.queue_keys = nullptr;
             sa.work_counter = counters + WS_SCANWORK;
-            sa.out6 = d_out6; sa.status = d_status; sa.best_adapter = d_best_adapter;
+            sa.out6 = c.d_out6; sa.status = c.d_status; sa.best_adapter = c.d_best_adapter;
             sa.adapter_index = 0; sa.merge_best = 1;
-            sa.pairs = d_pairs; sa.tab = pd->d_mscan; sa.n_adapters = (int32_t)A; sa.multi_skip_ok = mp.hdr.skip_ok;
-            sa.best_key = d_best_key;
-            sa.dp_queue = d_dpq; sa.dp_win = d_win;
+            sa.pairs = c.sc.pairs; sa.tab = pd->d_mscan; sa.n_adapters = (int32_t)A; sa.multi_skip_ok = mp.hdr.skip_ok;
+            sa.best_key = c.sc.best_key;
+            sa.dp_queue = c.sc.dpq; sa.dp_win = c.sc.win;
             sa.dp_count_front = counters + WS_DPFRONT; sa.dp_count_back = counters + WS_DPBACK;
             sa.dp_cap = cap;
             sa.retry_threshold = 0; sa.retry_queue = nullptr; sa.retry_keys = nullptr; sa.retry_count = nullptr;
             sa.retry_cap = 0; sa.queue_limit = 0; sa.early_stop = 0; sa.tile = 0;
-            sa.kind = scan_word_kind(plan->matchers[0].m);         // all adapters of the fused path have one shape
+            sa.kind = scan_word_kind(c.plan->matchers[0].m);       // all adapters of the fused path have one shape
             ProfScope ps(s, CAH_PROF_SCAN, cnt);
             HIP_TRY(launch_back_scan(sa, cnt * A, pd->n_cus, s));
         }
@@ -1883,29 +1767,52 @@ static int match_batch_multi_once(const cah_plan* plan, const PlanDeviceCopy* pd
             DpArgs a;
             a.uniform_first = ulo.first; a.uniform_len = ulo.len;
             a.matcher = pd->d_matchers;
-            a.seqs = d_seqs; a.offsets = d_offsets; a.lens = d_lens; a.n_reads = cnt * A;
+            a.seqs = c.d_seqs; a.offsets = c.d_offsets; a.lens = c.d_lens; a.n_reads = cnt * A;
             a.max_read_len = CAH_MAX_READ_LEN;
-            a.queue = d_dpq; a.queue_count = counters + WS_DPFRONT; a.queue_keys = nullptr;
+            a.queue = c.sc.dpq; a.queue_count = counters + WS_DPFRONT; a.queue_keys = nullptr;
             a.work_counter = counters + WS_DPWORK;
-            a.out6 = d_out6; a.status = d_status; a.best_adapter = d_best_adapter;
+            a.out6 = c.d_out6; a.status = c.d_status; a.best_adapter = c.d_best_adapter;
             a.adapter_index = 0; a.merge_best = 1;
-            a.win = d_win; a.queue_count_back = counters + WS_DPBACK; a.queue_cap = cap;
-            a.pairs = d_pairs; a.tab = pd->d_mrow; a.n_adapters = (int32_t)A; a.best_key = d_best_key;
+            a.win = c.sc.win; a.queue_count_back = counters + WS_DPBACK; a.queue_cap = cap;
+            a.pairs = c.sc.pairs; a.tab = pd->d_mrow; a.n_adapters = (int32_t)A; a.best_key = c.sc.best_key;
             ProfScope ps(s, CAH_PROF_DP, cnt);
-            HIP_TRY(launch_dp(a, m0.m, true, true, cnt * A, pd->n_cus, s));
+            HIP_TRY(launch_dp(a, c.plan->matchers[0].m, true, true, cnt * A, pd->n_cus, s));
         }
     }
-    ProfScope ps(s, CAH_PROF_MERGE, n_reads);
-    HIP_TRY(launch_multi_decode(d_best_key, n_reads, d_out6, d_status, d_best_adapter, pd->n_cus, s));
+    ProfScope ps(s, CAH_PROF_MERGE, c.n_reads);
+    HIP_TRY(launch_multi_decode(c.sc.best_key, c.n_reads, c.d_out6, c.d_status, c.d_best_adapter, pd->n_cus, s));
     return CAH_OK;
 }
 
+static int match_batch_multi_once(const MultiCall& c, int path) {
+    HIP_TRY(hipMemsetAsync(c.sc.best_key, 0, sizeof(unsigned long long) * (size_t)c.n_reads, c.s));
+    return path == CAH_MULTI_STREAM ? run_multi_stream(c) : run_multi_fused(c);
+}
+// (a wave that gave up waiting for its tile -- err bit 1: nothing is wrong with the batch, the device was busy with
+// something else for seconds -- is no reason to fail the call: the batch is matched once more from the start)
+// route: the FUSED or STREAM route of this batch (multi_route.h); `extra` is the scratch behind the base workspace
+static int match_batch_multi(const cah_plan* plan, const PlanDeviceCopy* pd, const uint8_t* d_seqs,
+                             const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads, int32_t* d_out6,
+                             int32_t* d_best_adapter, uint8_t* d_status, const Workspace& ws, char* extra,
+                             hipStream_t s, const MultiRoute& route) {
+    const int64_t cap = multi_pair_cap(plan, n_reads);
+    const MultiCall c{plan, pd, d_seqs, d_offsets, d_lens, n_reads, d_out6, d_best_adapter, d_status, ws.counters, s, route.ul,
+                      cap, MultiScratch(extra, cap, n_reads)};
+    t_m2_waited_in_vain = false;
+    int rc = match_batch_multi_once(c, route.path);
+    if (rc == CAH_EINTERNAL && t_m2_waited_in_vain) {
+        t_m2_waited_in_vain = false;
+        rc = match_batch_multi_once(c, route.path);
+    }
+    return rc;
+}
+
 static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const int64_t* d_offsets,
-                            const int32_t* d_lens, const UniformLayout ul_in, int64_t n_reads, int32_t* d_out6,
+                            const int32_t* d_lens, const UniformLayout ul, int64_t n_reads, int32_t* d_out6,
                             int32_t* d_best_adapter, uint8_t* d_status, void* d_workspace, size_t workspace_bytes,
                             void* stream, const FrontFuse* fuse = nullptr, const CallHints* hints = nullptr) {
     const bool outputs_ready = hints && hints->outputs_ready;
-    int rc = check_batch(plan, d_seqs, (ul_in.len > 0 && !ul_in.suffix) ? (const void*)d_seqs : (const void*)d_offsets, n_reads);
+    int rc = check_batch(plan, d_seqs, (ul.len > 0 && !ul.suffix) ? (const void*)d_seqs : (const void*)d_offsets, n_reads);
     if (rc) return rc;
     if (n_reads == 0) return CAH_OK;
     if (!d_out6 || !d_status) return fail(CAH_EINVAL, "output pointers are NULL");
@@ -1915,28 +1822,18 @@ static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const i
     const PlanDeviceCopy* pd = nullptr;
     rc = plan_on_device(plan, &pd);
     if (rc) return rc;
-    // (cah_match_batch_frames: views anywhere in the buffer with a frame length -- only the streaming multi-adapter form
-    // has a use for the frame; every other path takes them as the plain views they are)
-    // (... a single adapter's streaming prefilter likewise, adapter by adapter: run_filter)
-    const bool ws_multi = workspace_bytes >= cah_plan_workspace_bytes(plan, n_reads);
-    const bool multi_form = plan->multi.hdr.ok && ws_multi;
-    // A MIXED plan (build_multi_mixed) takes the multi-adapter path only where match_batch_multi_once streams: equally
-    // long reads of 16..160 characters, or views / frames of such a length; anything else is the per-adapter loop below
-    // (the layout match_batch_multi gets below: views keep theirs, a suffix-only layout is no uniform batch for it)
-    const UniformLayout ul_multi = (ul_in.inner && d_lens) ? ul_in : (ul_in.suffix ? UniformLayout() : ul_in);
-    // (groups of tables, build_multi_groups, are routed the same way: multi_streams asks every group and CAH_NO_MULTI_GROUPS)
-    const bool mixed_go = plan->multi.mixed && ws_multi && multi_streams(plan->multi, ul_multi, (const int64_t*)d_offsets, d_lens) &&
-                          !(env_flag("CAH_NO_MULTI_MIXED") && !plan->multi.groups_one_length) && !env_flag("CAH_NO_MULTI");
-    const UniformLayout ul = (ul_in.general && multi_form &&
-                              !(plan->multi.m2.hdr.ok && multi2_read_len_ok(plan->multi.m2.hdr, ul_in.len) && !env_flag("CAH_NO_MULTI2") &&
-                                !env_flag("CAH_NO_MULTI2_VIEWS")))
-                                 ? UniformLayout() : ul_in;
+    // which path takes the batch, and with which layout: decided here, once (multi_route.h has the table).  Only the
+    // streaming multi-adapter form has a use for a frame length (cah_match_batch_frames); the per-adapter loop below takes
+    // the caller's layout (a single adapter's streaming prefilter decides adapter by adapter: run_filter)
+    MultiBatch mb;
+    mb.ul = ul; mb.has_lens = d_lens != nullptr; mb.ws_fits = workspace_bytes >= cah_plan_workspace_bytes(plan, n_reads);
+    const MultiRoute route = multi_route(plan->multi, mb, plan->multi.form == M_NONE ? MultiSwitches() : multi_switches());
+    const bool multi_path = route.path != CAH_MULTI_SEQUENTIAL;
     const Workspace ws(d_workspace, n_reads, workspace_bytes);
     unsigned long long* counters = ws.counters;
     const UniformLayout ul_rest = ul.suffix ? UniformLayout() : ul;     // what every kernel but the prefilter sees
     // The result rows are zeroed by the first adapter's prefilter on its way through the batch when there is one
     // (FilterArgs::clear_out6: 24 B per read that would otherwise be a memset pass of its own), by a memset if not.
-    const bool multi_path = multi_form || mixed_go;
     int32_t first_aligner = -1;
     for (int32_t ad = 0; ad < (int32_t)plan->matchers.size() && first_aligner < 0; ad++)
         if (plan->matchers[(size_t)ad].kind != CAH_KIND_KMER_ONLY) first_aligner = ad;
@@ -1966,12 +1863,10 @@ static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const i
             d_batch_flag = counters + WS_UFLAG;
         }
     }
-    t_last_multi_path = CAH_MULTI_SEQUENTIAL;
+    t_last_multi_path = route.path;
     if (multi_path)
-        // (views inside the reads of a uniform batch -- ul.inner: d_offsets / d_lens are the views' starts and lengths -- go
-        // through with their layout: the streaming form takes them end-aligned, multi2.hip's RV form)
         return match_batch_multi(plan, pd, d_seqs, d_offsets, d_lens, n_reads, d_out6, d_best_adapter, d_status, ws,
-                                 (char*)d_workspace + cah_workspace_bytes(n_reads), s, (ul.inner && d_lens) ? ul : ul_rest);
+                                 (char*)d_workspace + cah_workspace_bytes(n_reads), s, route);
     for (int32_t ad = 0; ad < (int32_t)plan->matchers.size(); ad++) {
         const CahMatcher& mt = plan->matchers[(size_t)ad];
         if (mt.kind == CAH_KIND_KMER_ONLY) continue;

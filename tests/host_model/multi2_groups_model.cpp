@@ -9,6 +9,8 @@
 // the merged result with the oracle's kmers_present + locate of every adapter on the whole read.
 #include "multi2_mixed_model.cpp"
 
+#include "../../cutadapt_amd/csrc/multi_route.h"
+
 namespace {
 
 struct Plan {
@@ -33,16 +35,8 @@ Plan read_plan(const char* adapters, int A, const void* blobs, int32_t n_ref, co
         p.ref[(size_t)ref_adapter[i]].push_back({std::string(kp), ref_window[i]});
         kp += strlen(kp) + 1;
     }
-    // what api.cpp asks of the whole plan before it builds groups (multi_stream_eligible)
-    for (int a = 0; a < A; a++) if (p.mts[(size_t)a].m > p.mts[(size_t)p.longest].m) p.longest = a;
-    const CahMatcher& ml = p.mts[(size_t)p.longest];
-    p.k_of.resize((size_t)A);
-    for (int a = 0; a < A; a++) {
-        const CahMatcher& mt = p.mts[(size_t)a];
-        if (!mt.scan_ok || mt.kacc != mt.k || mt.min_overlap != ml.min_overlap) p.eligible = false;
-        for (int i = 0; i <= mt.m; i++) if (mt.thr_last[i] != ml.thr_last[i]) p.eligible = false;
-        p.k_of[(size_t)a] = mt.kacc;
-    }
+    // what api.cpp asks of the whole plan's matchers before it builds groups (multi_route.h, the product's own)
+    p.eligible = m2_matchers_eligible(p.mts.data(), A, p.longest, p.k_of);
     return p;
 }
 

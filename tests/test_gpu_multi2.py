@@ -498,6 +498,55 @@ def test_frames_of_short_and_odd_batches(hip, orc):
         B.FRAME_MIN_READS = old_min
 
 
+def test_frames_that_do_not_stream_are_plain_views(hip, orc):
+    """cah_match_batch_frames with a frame the streaming multi-adapter form does not take -- 200 characters, longer than any
+    table set allows, and 160 under CAH_NO_MULTI2_VIEWS=1: the call is served (CAH_OK) with the views as the plain views
+    they are, by the older fused kernels for a plan of one shape, by the per-adapter loop for a mixed plan, which has no
+    fused kernels behind it.  Rows against the oracle in full."""
+    import torch
+    from cutadapt_amd import _lib
+    from cutadapt_amd.batch import ReadBatch, _stream_ptr
+    prng = random.Random(94)
+    one_shape = [rs(prng, 20) for _ in range(8)]
+    mixed = [rs(prng, m) for m in (12, 16, 20, 24, 28, 33, 36, 40)]
+    reads = []
+    for i in range(2000):
+        ln = prng.randint(30, 200)
+        r = rs(prng, ln)
+        if i % 3 != 2:
+            ad = (one_shape + mixed)[i % 16]
+            cut = ad[: prng.randint(3, len(ad))]
+            r = r[: ln - len(cut)] + cut if i % 2 else (r[: ln - len(ad) - 5] + ad + r)[:ln]
+        reads.append(r)
+    # (the caller guarantees that no view is longer than its frame)
+    for frame, views_off, batch_reads in ((200, None, reads), (160, "1", [r for r in reads if len(r) <= 160])):
+        sq, offs = orc.pack_reads(batch_reads)
+        n = len(batch_reads)
+        for seqs, path in ((one_shape, "fused"), (mixed, "sequential")):
+            plan, ads = plan_for(seqs, 0.1, 3)
+            assert plan.multi_kind(160) == "stream" and plan.multi_kind(200) == path, (path, plan.multi_kind(160), plan.multi_kind(200))
+            batch = ReadBatch.from_host(sq, offs)
+            lens = (batch.offsets[1:] - batch.offsets[:-1]).to(torch.int32)
+            out6 = torch.empty((n, 6), dtype=torch.int32, device=batch.device)
+            status = torch.empty(n, dtype=torch.uint8, device=batch.device)
+            best = torch.empty(n, dtype=torch.int32, device=batch.device)
+            ws = batch.workspace(plan)
+            with env(CAH_NO_MULTI2_VIEWS=views_off):
+                rc = _lib.lib().cah_match_batch_frames(plan.handle, batch.seqs.data_ptr(), batch.offsets.data_ptr(), lens.data_ptr(),
+                                                       frame, n, out6.data_ptr(), best.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                                       ws.numel(), _stream_ptr())
+                torch.cuda.synchronize()
+                assert rc == 0, (frame, path, rc)
+                assert _lib.last_multi_path() == path, (frame, path, _lib.last_multi_path())
+            want6, want_st, want_best = oracle_multiple(orc, ads, sq, offs)
+            g6, gst = out6.cpu().numpy(), status.cpu().numpy()
+            bad = np.nonzero((gst != want_st) | (g6 != want6).any(axis=1))[0]
+            assert len(bad) == 0, (frame, path, len(bad), batch_reads[int(bad[0])], g6[bad[0]].tolist(), want6[bad[0]].tolist())
+            fw = want_st == 1
+            assert np.array_equal(best.cpu().numpy()[fw], want_best[fw]), (frame, path)
+            assert int(fw.sum()) > 0.3 * n
+
+
 def test_characters_that_read_as_A_in_the_lookup_words(hip, orc):
     """The tables are looked up with two bits per character: anything but A / C / G / T -- an N, the NULs in front of a view in
     its frame -- reads as 'A' there (multi2.h: m2_roll2).  Adapters rich in A then meet k-mers everywhere in such reads: pairs

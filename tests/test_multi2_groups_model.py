@@ -33,7 +33,7 @@ REFUSED_NOT, REFUSED_CAPACITY, REFUSED_RULE = 0, 1, 2           # multi2.h: M2_R
 @pytest.fixture(scope="module")
 def groups_model():
     deps = [SRC] + [os.path.join(HERE, "host_model", f) for f in ("back_model.cpp", "multi2_model.cpp", "multi2_mixed_model.cpp")] + \
-           [os.path.join(CSRC, h) for h in ("back_scan.h", "cah_device.h", "multi2.h")]
+           [os.path.join(CSRC, h) for h in ("back_scan.h", "cah_device.h", "multi2.h", "multi_route.h")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", SRC, "-o", SO], check=True)
     L = C.CDLL(SO)
