@@ -180,7 +180,24 @@ int cah_locate_batch(const cah_plan *plan, int32_t adapter, const uint8_t *d_seq
                      int32_t *d_out6, uint8_t *d_status, void *d_workspace,
                      size_t workspace_bytes, void *stream);
 
-/* KmerFinder.kmers_present over a batch: d_present[r] = 0 / 1 (or CAH_INVALID). */
+/* KmerFinder.kmers_present over a batch (reference _kmer_finder.pyx:170-257); all pointers are device pointers, the
+ * call returns after the kernel has finished.
+ *   d_lens == NULL: read r is d_seqs[d_offsets[r] .. d_offsets[r + 1]) and d_offsets holds n_reads + 1 entries;
+ *   d_lens != NULL: read r is the view d_seqs[d_offsets[r] .. d_offsets[r] + d_lens[r]) and d_offsets holds n_reads
+ *                   entries.  Any base address and any offsets: nothing needs to be aligned.
+ * The window of every search set is computed per read as _kmer_finder.pyx:186-204 does -- negative start and stop count
+ * from the read's end, start > length and stop + length <= 0 search nothing -- and a positive stop beyond the read's end
+ * is clamped to it (the reference reads out of bounds there).  No byte outside a read is looked at: what lies in front
+ * of, between and behind the reads changes nothing, bytes >= 0x80 included.
+ * Every row r < n_reads is written, no other row:
+ *   1            some k-mer of a search set occurs inside the set's window;
+ *   0            none does;
+ *   CAH_INVALID  the read is longer than CAH_MAX_READ_LEN, or no k-mer occurs in its window and a byte >= 0x80 lies
+ *                inside the union of the read's windows.  That much every prefilter kernel guarantees.  A byte >= 0x80
+ *                inside the read but outside every window, or behind the first occurrence, may or may not be reported
+ *                (the kernels differ in how much of a read they walk): cah_validate_ascii_batch checks whole reads.
+ * n_reads == 0 returns CAH_OK and writes nothing.  A plan whose search sets pack into more than 1024 words is
+ * CAH_EUNSUPPORTED; nothing is launched and no row is written. */
 int cah_kmers_present_batch(const cah_plan *plan, int32_t adapter, const uint8_t *d_seqs,
                             const int64_t *d_offsets, const int32_t *d_lens, int64_t n_reads,
                             uint8_t *d_present, void *stream);
