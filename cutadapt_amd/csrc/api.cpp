@@ -929,6 +929,39 @@ static void build_multi(const cah_adapter_desc* descs, int n, cah_plan* plan) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// a batch, as the entry points below hand it down
+// ---------------------------------------------------------------------------------------------
+// What a call works on, described ONCE and handed down as it is (the launch structs of kernels.h are filled from these by
+// fill_reads / fill_results; whatever a site does not set keeps its default there, which means "not used"):
+//   Reads     the batch: read r = seqs[offsets[r] ..) of lens[r] (or offsets[r + 1] - offsets[r]) characters, and what the
+//             host knows about its layout (multi_route.h: UniformLayout)
+//   Results   where the rows, the status bytes and (may be NULL) the best adapter of every read go
+//   WorkList  the reads a kernel works on: the prefilter's survivors with their count and keys; empty: all reads
+struct Reads {
+    const uint8_t* seqs = nullptr; const int64_t* offsets = nullptr; const int32_t* lens = nullptr;
+    int64_t n = 0;
+    UniformLayout ul;
+    Reads with(const UniformLayout& other) const { Reads r = *this; r.ul = other; return r; }
+};
+struct Results { int32_t* out6 = nullptr; uint8_t* status = nullptr; int32_t* best = nullptr; };
+struct WorkList { int32_t* queue = nullptr; unsigned long long* count = nullptr; uint8_t* keys = nullptr; };
+
+template <class Args> static void fill_reads(Args& a, const Reads& r) {
+    a.uniform_first = r.ul.first; a.uniform_len = r.ul.len;
+    a.seqs = r.seqs; a.offsets = r.offsets; a.lens = r.lens; a.n_reads = r.n;
+    a.max_read_len = CAH_MAX_READ_LEN;
+}
+template <class Args> static void fill_results(Args& a, const Results& o, int32_t adapter_index, int32_t merge_best) {
+    a.out6 = o.out6; a.status = o.status; a.best_adapter = o.best;
+    a.adapter_index = adapter_index; a.merge_best = merge_best;
+}
+// Multi2Args / Multi2ScanArgs: the batch is uniform (no offsets / lens); views inside its reads travel as view_*
+template <class Args> static void fill_stream_reads(Args& a, const Reads& r, bool views) {
+    a.uniform_first = r.ul.first; a.uniform_len = r.ul.len; a.seqs = r.seqs;
+    if (views) { a.view_starts = r.offsets; a.view_lens = r.lens; a.view_general = r.ul.general ? 1 : 0; }
+}
+
 extern "C" {
 
 int cah_abi_version(void) { return CAH_ABI_VERSION; }
@@ -1273,6 +1306,11 @@ static int check_batch(const cah_plan* plan, const void* d_seqs, const void* d_o
     (void)d_seqs;
     return CAH_OK;
 }
+// ... of the entry points that name ONE adapter of the plan
+static int check_batch(const cah_plan* plan, int32_t adapter, const void* d_seqs, const void* d_offsets, int64_t n_reads) {
+    if (int rc = check_batch(plan, d_seqs, d_offsets, n_reads)) return rc;
+    return check_adapter(plan, adapter);
+}
 
 // Tiny batches (the per-read calls of the Python mirror classes send batches of one) are launch-bound: what a caller
 // has already done for the callee travels as explicit arguments (no per-thread state between entry points):
@@ -1322,40 +1360,29 @@ static int64_t scan_retry_cap(int64_t cap) {
     return x < 1 ? 1 : (x < cap ? x : cap);
 }
 
-// Aligner / comparer over a work list (d_queue == NULL: all reads).  3' adapters with unit costs go
-// through the cost scan first (k_back_scan finishes most reads, the rest reach k_dp_packed with an exact
-// column window); everything else runs the cell kernel directly.
-// equally long reads the host vouches for (cah_match_batch_uniform): read r = d_seqs[first + r * len ..); len == 0: the
-// packed layout (offsets / lens)
 // cah_linked_match_batch_uniform, fused form: the streaming prefilter of the back adapter decides the views itself
 // (kernels.h: FilterArgs::front) and writes the front stage's outputs and the views
 struct FrontFuse {
     const CahMatcher* d_matcher = nullptr;
-    int32_t* out6 = nullptr;
-    uint8_t* status = nullptr;
-    int32_t* best = nullptr;
+    Results front;
     int64_t* starts = nullptr;
     int32_t* lens = nullptr;
 };
 
-static int run_aligner(const cah_plan* plan, const PlanDeviceCopy* pd, int32_t adapter, const uint8_t* d_seqs,
-                       const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads,
-                       const int32_t* d_queue, const unsigned long long* d_queue_count,
-                       const uint8_t* d_queue_keys, const Workspace& ws, int32_t* d_out6,
-                       uint8_t* d_status, int32_t* d_best, int merge_best, hipStream_t s,
-                       const UniformLayout ul = UniformLayout(), const bool header_fresh = false) {
+// Aligner / comparer over a work list (empty: all reads).  3' adapters with unit costs go
+// through the cost scan first (k_back_scan finishes most reads, the rest reach k_dp_packed with an exact
+// column window); everything else runs the cell kernel directly.
+static int run_aligner(const cah_plan* plan, const PlanDeviceCopy* pd, int32_t adapter, const Reads& r, const WorkList& wl,
+                       const Workspace& ws, const Results& out, int merge_best, hipStream_t s,
+                       const bool header_fresh = false) {
     const CahMatcher& mt = plan->matchers[(size_t)adapter];
+    const int64_t n_reads = r.n;
     DpArgs a;
-    a.uniform_first = ul.first; a.uniform_len = ul.len;
+    fill_reads(a, r);
+    fill_results(a, out, adapter, merge_best);
     a.matcher = pd->d_matchers + adapter;
-    a.seqs = d_seqs; a.offsets = d_offsets; a.lens = d_lens; a.n_reads = n_reads;
-    a.max_read_len = CAH_MAX_READ_LEN;
-    a.queue = d_queue; a.queue_count = d_queue_count; a.queue_keys = d_queue_keys;
+    a.queue = wl.queue; a.queue_count = wl.count; a.queue_keys = wl.keys;
     a.work_counter = ws.counters + WS_DPWORK;
-    a.out6 = d_out6; a.status = d_status; a.best_adapter = d_best;
-    a.adapter_index = adapter; a.merge_best = merge_best;
-    a.win = nullptr; a.queue_count_back = nullptr; a.queue_cap = 0;
-    a.pairs = nullptr; a.tab = nullptr; a.n_adapters = 0; a.best_key = nullptr;
     // DP work counter, scan tile counter, DP list counts: one memset over their lines
     if (!header_fresh)
         HIP_TRY(hipMemsetAsync(ws.counters + WS_DPWORK, 0, WS_HEADER - WS_DPWORK * sizeof(unsigned long long), s));
@@ -1369,13 +1396,11 @@ static int run_aligner(const cah_plan* plan, const PlanDeviceCopy* pd, int32_t a
                         mt.m, cah_plan_workspace_bytes(plan, n_reads));
         const LongDeviceCopy& ld = pd->d_long[(size_t)adapter];
         LongArgs la;
-        la.uniform_first = ul.first; la.uniform_len = ul.len;
+        fill_reads(la, r);
+        fill_results(la, out, adapter, merge_best);
         la.lm = ld.d_lm; la.ref = ld.d_ref; la.ncnt = ld.d_ncnt;
-        la.seqs = d_seqs; la.offsets = d_offsets; la.lens = d_lens; la.n_reads = n_reads; la.max_read_len = CAH_MAX_READ_LEN;
-        la.queue = d_queue; la.queue_count = d_queue_count; la.work_counter = ws.counters + WS_DPWORK;
+        la.queue = wl.queue; la.queue_count = wl.count; la.work_counter = ws.counters + WS_DPWORK;
         la.scratch = (int32_t*)ws.extra;
-        la.out6 = d_out6; la.status = d_status; la.best_adapter = d_best; la.adapter_index = adapter; la.merge_best = merge_best;
-        la.dbg_cost = nullptr; la.dbg_score = nullptr;
         ProfScope ps(s, mt.kind == CAH_KIND_ALIGNER ? CAH_PROF_DP : CAH_PROF_COMPARER, n_reads);
         HIP_TRY(launch_dp_long(la, lanes, s));
         return CAH_OK;
@@ -1389,15 +1414,11 @@ static int run_aligner(const cah_plan* plan, const PlanDeviceCopy* pd, int32_t a
     if (mt.kind == CAH_KIND_ALIGNER) {
         if (mt.scan_ok) {
             ScanArgs sa;
-            sa.uniform_first = ul.first; sa.uniform_len = ul.len;
+            fill_reads(sa, r);
+            fill_results(sa, out, adapter, merge_best);
             sa.matcher = a.matcher;
-            sa.seqs = d_seqs; sa.offsets = d_offsets; sa.lens = d_lens; sa.n_reads = n_reads;
-            sa.max_read_len = CAH_MAX_READ_LEN;
-            sa.queue = d_queue; sa.queue_count = d_queue_count; sa.queue_keys = d_queue_keys;
+            sa.queue = wl.queue; sa.queue_count = wl.count; sa.queue_keys = wl.keys;
             sa.work_counter = ws.counters + WS_SCANWORK;
-            sa.out6 = d_out6; sa.status = d_status; sa.best_adapter = d_best;
-            sa.adapter_index = adapter; sa.merge_best = merge_best;
-            sa.pairs = nullptr; sa.tab = nullptr; sa.n_adapters = 0; sa.multi_skip_ok = 0; sa.best_key = nullptr;
             sa.dp_queue = ws.dp_queue; sa.dp_win = ws.dp_win;
             sa.dp_count_front = ws.counters + WS_DPFRONT; sa.dp_count_back = ws.counters + WS_DPBACK;
             sa.dp_cap = n_reads;
@@ -1405,9 +1426,8 @@ static int run_aligner(const cah_plan* plan, const PlanDeviceCopy* pd, int32_t a
             // batches are launch-bound and keep the single launch
             sa.retry_threshold = n_reads > 4096 ? scan_retry_threshold() : 0;
             sa.retry_queue = ws.retry_queue; sa.retry_keys = ws.retry_keys; sa.retry_cap = scan_retry_cap(ws.retry_cap);
-            sa.retry_count = ws.counters + WS_RETRYCOUNT; sa.queue_limit = 0;
-            sa.early_stop = d_queue != nullptr && d_queue_keys != nullptr;
-            sa.tile = 0;
+            sa.retry_count = ws.counters + WS_RETRYCOUNT;
+            sa.early_stop = wl.queue != nullptr && wl.keys != nullptr;
             sa.kind = scan_word_kind(mt.m);
             {
                 ProfScope ps(s, CAH_PROF_SCAN, n_reads);
@@ -1438,9 +1458,7 @@ int cah_locate_batch(const cah_plan* plan, int32_t adapter, const uint8_t* d_seq
                      const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads,
                      int32_t* d_out6, uint8_t* d_status, void* d_workspace, size_t workspace_bytes,
                      void* stream) {
-    int rc = check_batch(plan, d_seqs, d_offsets, n_reads);
-    if (rc) return rc;
-    rc = check_adapter(plan, adapter);
+    int rc = check_batch(plan, adapter, d_seqs, d_offsets, n_reads);
     if (rc) return rc;
     if (plan->matchers[(size_t)adapter].kind == CAH_KIND_KMER_ONLY)
         return fail(CAH_EINVAL, "adapter %d has no aligner", adapter);
@@ -1452,8 +1470,9 @@ int cah_locate_batch(const cah_plan* plan, int32_t adapter, const uint8_t* d_seq
     const PlanDeviceCopy* pd = nullptr;
     rc = plan_on_device(plan, &pd);
     if (rc) return rc;
-    return run_aligner(plan, pd, adapter, d_seqs, d_offsets, d_lens, n_reads, nullptr, nullptr, nullptr,
-                       ws, d_out6, d_status, nullptr, 0, (hipStream_t)stream);      // (its one memset is the header's)
+    const Reads reads{d_seqs, d_offsets, d_lens, n_reads};
+    return run_aligner(plan, pd, adapter, reads, WorkList(), ws, Results{d_out6, d_status}, 0,
+                       (hipStream_t)stream);                                        // (its one memset is the header's)
 }
 
 // can the streaming prefilter take views that are suffixes of a uniform batch's reads (k_filter_stream2, SV form)?
@@ -1463,53 +1482,54 @@ static bool stream2_suffix_ok(const cah_plan* plan, int32_t adapter, int32_t len
            n_reads * (int64_t)len >= 16 && !env_flag("CAH_NO_STREAM") && !env_flag("CAH_NO_STREAM2");
 }
 
-static int run_filter(const cah_plan* plan, const PlanDeviceCopy* pd, int32_t adapter, const uint8_t* d_seqs,
-                      const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads, int mode,
-                      uint8_t* d_present, uint8_t* d_status, int32_t* d_queue,
-                      unsigned long long* d_queue_count, uint8_t* d_queue_keys,
-                      unsigned long long* d_work_counter, const unsigned long long* d_batch_flag, hipStream_t s,
-                      int32_t* d_clear_out6 = nullptr, int32_t* d_clear_best = nullptr,
-                      const UniformLayout ul = UniformLayout(), const FrontFuse* fuse = nullptr,
-                      const bool header_fresh = false) {
+// what run_filter does besides filtering: nothing, unless the call site names it
+struct FilterOpts {
+    Results clear;                       // mode 1: out6 (and best) of every read the kernel looks at are cleared on the way (FilterArgs::clear_out6)
+    const FrontFuse* fuse = nullptr;
+    bool header_fresh = false;           // (CallHints)
+};
+
+// mode 0: present[r] for every read; mode 1: the survivors go to `wl`, the status of invalid reads to d_status
+static int run_filter(const cah_plan* plan, const PlanDeviceCopy* pd, int32_t adapter, const Reads& r, int mode,
+                      uint8_t* d_present, uint8_t* d_status, const WorkList& wl, unsigned long long* d_work_counter,
+                      const unsigned long long* d_batch_flag, hipStream_t s, const FilterOpts& opt = FilterOpts()) {
     const CahMatcher& mt = plan->matchers[(size_t)adapter];
+    const UniformLayout& ul = r.ul;
+    const int64_t n_reads = r.n;
     if (mt.n_words > 1024)
         return fail(CAH_EUNSUPPORTED, "adapter %d: %d packed k-mer words exceed the 1024-word limit of the prefilter kernel",
                     adapter, mt.n_words);
     FilterArgs f;
+    fill_reads(f, r);
     f.words = pd->d_words + mt.first_word;
     f.n_words = mt.n_words;
-    f.seqs = d_seqs; f.offsets = d_offsets; f.lens = d_lens; f.n_reads = n_reads;
-    f.max_read_len = CAH_MAX_READ_LEN;
     f.work_counter = d_work_counter;
-    f.present = d_present; f.status = d_status; f.queue = d_queue; f.queue_count = d_queue_count;
-    f.queue_keys = d_queue_keys;
-    f.batch_flag = nullptr;
-    f.lean = nullptr;
-    f.stream_n_lo = 0; f.stream_n_hi = -1;
-    f.uniform_first = ul.first; f.uniform_len = ul.len;
+    f.present = d_present; f.status = d_status; f.queue = wl.queue; f.queue_count = wl.count;
+    f.queue_keys = wl.keys;
     if (ul.suffix) {
         // views into a uniform parent: k_filter_stream2's SV form if the plan and the length are its, else plain views
         const bool s2 = stream2_suffix_ok(plan, adapter, ul.len, n_reads);
         f.suffix_views = s2 ? (ul.general ? 3 : (ul.inner ? 2 : 1)) : 0;     // (3: views anywhere, frames of ul.len characters)
         if (!s2) { f.uniform_first = 0; f.uniform_len = 0; }
-        if (fuse) {
+        if (opt.fuse) {
             if (!s2) return fail(CAH_EINVAL, "internal: fused linked path on a plan the streaming prefilter does not take");
-            f.front = fuse->d_matcher; f.front_out6 = fuse->out6; f.front_status = fuse->status; f.front_best = fuse->best;
-            f.view_starts = fuse->starts; f.view_lens = fuse->lens;
+            const FrontFuse& fu = *opt.fuse;
+            f.front = fu.d_matcher; f.front_out6 = fu.front.out6; f.front_status = fu.front.status; f.front_best = fu.front.best;
+            f.view_starts = fu.starts; f.view_lens = fu.lens;
         }
     }
-    f.clear_out6 = mode == 1 ? d_clear_out6 : nullptr;
-    f.clear_best = f.clear_out6 ? d_clear_best : nullptr;
-    if (!header_fresh) {
+    f.clear_out6 = mode == 1 ? opt.clear.out6 : nullptr;
+    f.clear_best = f.clear_out6 ? opt.clear.best : nullptr;
+    if (!opt.header_fresh) {
         HIP_TRY(hipMemsetAsync(d_work_counter, 0, sizeof(unsigned long long), s));
-        if (d_queue_count) HIP_TRY(hipMemsetAsync(d_queue_count, 0, sizeof(unsigned long long), s));
+        if (wl.count) HIP_TRY(hipMemsetAsync(wl.count, 0, sizeof(unsigned long long), s));
     }
     ProfScope ps(s, CAH_PROF_FILTER, n_reads);
     if (plan->lean[(size_t)adapter].ok) {
         // 3' adapter plans: k_filter_lean.  For a packed batch the device-side batch check (*d_batch_flag)
         // picks its equal-length or its ragged variant -- both are launched, one leaves at once, no host
         // sync; views (explicit lengths) and calls without a check take the ragged variant.
-        f.batch_flag = (d_lens || f.uniform_len > 0) ? nullptr : d_batch_flag;
+        f.batch_flag = (r.lens || f.uniform_len > 0) ? nullptr : d_batch_flag;
         f.lean = pd->d_lean + adapter;
         const CahLeanFilter& lf = plan->lean[(size_t)adapter];
         HIP_TRY(launch_filter_lean(f, mode, lf.n_lead, lf.n_gated, lf.lead_delay, lf.tw_ok, lf.n_tw, pd->n_cus, s));
@@ -1522,9 +1542,7 @@ static int run_filter(const cah_plan* plan, const PlanDeviceCopy* pd, int32_t ad
 int cah_kmers_present_batch(const cah_plan* plan, int32_t adapter, const uint8_t* d_seqs,
                             const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads,
                             uint8_t* d_present, void* stream) {
-    int rc = check_batch(plan, d_seqs, d_offsets, n_reads);
-    if (rc) return rc;
-    rc = check_adapter(plan, adapter);
+    int rc = check_batch(plan, adapter, d_seqs, d_offsets, n_reads);
     if (rc) return rc;
     if (n_reads == 0) return CAH_OK;
     if (!d_present) return fail(CAH_EINVAL, "present is NULL");
@@ -1548,8 +1566,8 @@ int cah_kmers_present_batch(const cah_plan* plan, int32_t adapter, const uint8_t
         HIP_TRY(hipMalloc((void**)&t_counter, 256));
         t_counter_device = dev;
     }
-    rc = run_filter(plan, pd, adapter, d_seqs, d_offsets, d_lens, n_reads, 0, d_present, nullptr, nullptr,
-                    nullptr, nullptr, t_counter, nullptr, s);
+    rc = run_filter(plan, pd, adapter, Reads{d_seqs, d_offsets, d_lens, n_reads}, 0, d_present, nullptr, WorkList(),
+                    t_counter, nullptr, s);
     hipError_t e = hipStreamSynchronize(s);
     if (rc) return rc;
     if (e != hipSuccess) return fail(CAH_EHIP, "k_filter failed: %s", hipGetErrorString(e));
@@ -1577,9 +1595,8 @@ static thread_local bool t_m2_waited_in_vain = false;     // the last failure of
 // what one call of the multi-adapter path works on; ul: the layout its route gives the path (multi_route.h)
 struct MultiCall {
     const cah_plan* plan; const PlanDeviceCopy* pd;
-    const uint8_t* d_seqs; const int64_t* d_offsets; const int32_t* d_lens; int64_t n_reads;
-    int32_t* d_out6; int32_t* d_best_adapter; uint8_t* d_status;
-    unsigned long long* counters; hipStream_t s; UniformLayout ul;
+    Reads reads; Results out;
+    unsigned long long* counters; hipStream_t s;
     int64_t cap;                                             // multi_pair_cap: the pairs the scratch has room for
     MultiScratch sc;
 };
@@ -1600,10 +1617,10 @@ static bool m2_ungated() {
 static int run_stream_group(const MultiCall& c, int g, int64_t lo, int64_t cnt, bool deferred) {
     const MultiPlan& mp = c.plan->multi;
     const PlanDeviceCopy* pd = c.pd;
-    const UniformLayout& ul = c.ul;
+    const UniformLayout& ul = c.reads.ul;
     hipStream_t s = c.s;
     unsigned long long* counters = c.counters;
-    const bool views = ul.inner && c.d_lens != nullptr && c.d_offsets != nullptr;    // views inside the reads of a uniform batch
+    const bool views = ul.inner && c.reads.lens != nullptr && c.reads.offsets != nullptr;    // views inside the reads of a uniform batch
     // the pool: pages of CAH_M2_PAGE pairs + one header word each, inside the pair area
     const int64_t max_pages = m2_pool_pages(c.cap), open_pages = 16 * CAH_M2_PAIR_CLASSES;
     uint32_t* d_page_hdr = (uint32_t*)(c.sc.pairs + max_pages * CAH_M2_PAGE);
@@ -1644,35 +1661,33 @@ static int run_stream_group(const MultiCall& c, int g, int64_t lo, int64_t cnt, 
         const int64_t units = (round || g) ? -1 : cnt;
         {
             Multi2Args f;
-            f.uniform_first = ul.first; f.uniform_len = ul.len;
+            fill_stream_reads(f, c.reads, views);
             f.win_hi = tb.hdr.win_dist[M2_HI]; f.win_lo = tb.hdr.win_dist[M2_LO];
             f.hdr = dt.d_m2hdr; f.dir = dt.d_m2dir; f.entries = dt.d_m2entries; f.bitmap = dt.d_m2bitmap;
             f.prefix = dt.d_m2prefix;
-            f.seqs = c.d_seqs; f.first_read = lo; f.n_reads = cnt; f.status = c.d_status; f.best_key = c.sc.best_key;
+            f.first_read = lo; f.n_reads = cnt; f.status = c.out.status; f.best_key = c.sc.best_key;
             f.pairs = c.sc.pairs; f.page_hdr = d_page_hdr; f.page_counter = counters + WS_QCOUNT; f.max_pages = max_pages;
             f.tile_counter = counters + WS_M2_TILE; f.n_tiles = n_tiles; f.gate_pages = sh.gate;
             f.err = counters + WS_M2_ERR;
             f.wmeta = c.sc.wmeta;
             f.adapter_base = base;
-            if (views) { f.view_starts = c.d_offsets; f.view_lens = c.d_lens; f.view_general = ul.general ? 1 : 0; }
             ProfScope ps(s, CAH_PROF_FILTER, units);
             HIP_TRY(launch_multi_stream(f, tb.hdr, (int)sh.grid, s));
         }
         {
             Multi2ScanArgs sa;
-            sa.uniform_first = ul.first; sa.uniform_len = ul.len;
+            fill_stream_reads(sa, c.reads, views);
             sa.kind = scan_word_kind(mlong.m);
             if (g_mixed) { sa.mixed = 1; sa.longest = mp.group_longest(g); sa.kind = scan_word_kind(mlong.m) == 1 ? 1 : 0; }
             sa.rows_lo = tb.hdr.rows_lo;
             sa.matcher = pd->d_matchers + base; sa.tab = pd->d_mscan + (size_t)base * CAH_MULTI_TAB_STRIDE; sa.n_adapters = (int32_t)Ag;
-            sa.seqs = c.d_seqs; sa.pairs = c.sc.pairs; sa.page_hdr = d_page_hdr;
+            sa.pairs = c.sc.pairs; sa.page_hdr = d_page_hdr;
             sa.page_counter = counters + WS_QCOUNT; sa.max_pages = max_pages; sa.err = counters + WS_M2_ERR;
             sa.work_counter = counters + WS_SCANWORK; sa.best_key = c.sc.best_key;
             sa.dp_queue = c.sc.dpq; sa.dp_win = c.sc.win;
             sa.dp_count_front = counters + WS_DPFRONT; sa.dp_count_back = counters + WS_DPBACK; sa.dp_cap = c.cap;
             sa.wmeta = c.sc.wmeta; sa.prefix = dt.d_m2prefix; sa.lmax0 = tb.hdr.lmax0;
             sa.adapter_base = base;
-            if (views) { sa.view_starts = c.d_offsets; sa.view_lens = c.d_lens; sa.view_general = ul.general ? 1 : 0; }
             // (how many pages there are is known on the device only: the blocks draw pages until none is left)
             ProfScope ps(s, CAH_PROF_SCAN, units);
             HIP_TRY(launch_multi_scan(sa, std::min(max_pages, n_tiles * per_tile + sh.grid * open_pages), pd->n_cus, s));
@@ -1680,13 +1695,11 @@ static int run_stream_group(const MultiCall& c, int g, int64_t lo, int64_t cnt, 
         {
             // the cell DP over the pairs the scan left (the launch returns at once when there are none)
             DpArgs a;
-            a.uniform_first = ul.first; a.uniform_len = views ? 0 : ul.len;     // (views: the cell DP reads starts + lengths)
+            fill_reads(a, c.reads);
+            fill_results(a, c.out, 0, 1);
+            if (views) a.uniform_len = 0;                                       // (views: the cell DP reads starts + lengths)
+            a.n_reads = cnt * Ag;
             a.matcher = pd->d_matchers + base;
-            a.seqs = c.d_seqs; a.offsets = c.d_offsets; a.lens = c.d_lens; a.n_reads = cnt * Ag;
-            a.max_read_len = CAH_MAX_READ_LEN;
-            a.queue_keys = nullptr;
-            a.out6 = c.d_out6; a.status = c.d_status; a.best_adapter = c.d_best_adapter;
-            a.adapter_index = 0; a.merge_best = 1;
             a.pairs = c.sc.pairs; a.tab = pd->d_mrow + (size_t)base * CAH_MULTI_TAB_STRIDE; a.n_adapters = (int32_t)Ag; a.best_key = c.sc.best_key;
             a.queue = c.sc.dpq; a.queue_count = counters + WS_DPFRONT; a.queue_count_back = counters + WS_DPBACK;
             a.win = c.sc.win; a.queue_cap = c.cap; a.work_counter = counters + WS_DPWORK;
@@ -1706,15 +1719,16 @@ static int run_multi_stream(const MultiCall& c) {
     // (pairs carry the read's index in 32 bits, the prefilter counts reads in an int)
     const int64_t BLOCK = (int64_t)1 << 30;
     // (the deferred form: nothing for the host to decide in ANY group, known before the first group runs)
-    const bool deferred = t_deferred_errors && c.n_reads <= BLOCK &&
-                          m2_one_launch_for_all(mp, (int)c.plan->matchers.size(), c.n_reads, m2_pool_pages(c.cap), c.pd->n_cus, m2_ungated());
-    for (int64_t lo = 0; lo < c.n_reads; lo += BLOCK)
+    const int64_t n_reads = c.reads.n;
+    const bool deferred = t_deferred_errors && n_reads <= BLOCK &&
+                          m2_one_launch_for_all(mp, (int)c.plan->matchers.size(), n_reads, m2_pool_pages(c.cap), c.pd->n_cus, m2_ungated());
+    for (int64_t lo = 0; lo < n_reads; lo += BLOCK)
         for (int g = 0; g < mp.n_tables(); g++) {
-            const int rc = run_stream_group(c, g, lo, std::min(BLOCK, c.n_reads - lo), deferred);
+            const int rc = run_stream_group(c, g, lo, std::min(BLOCK, n_reads - lo), deferred);
             if (rc) return rc;
         }
-    ProfScope ps(c.s, CAH_PROF_MERGE, c.n_reads);
-    HIP_TRY(launch_multi_decode(c.sc.best_key, c.n_reads, c.d_out6, c.d_status, c.d_best_adapter, c.pd->n_cus, c.s,
+    ProfScope ps(c.s, CAH_PROF_MERGE, n_reads);
+    HIP_TRY(launch_multi_decode(c.sc.best_key, n_reads, c.out.out6, c.out.status, c.out.best, c.pd->n_cus, c.s,
                                 deferred ? c.counters + WS_M2_ERR : nullptr));
     return CAH_OK;
 }
@@ -1723,81 +1737,70 @@ static int run_multi_stream(const MultiCall& c) {
 static int run_multi_fused(const MultiCall& c) {
     const MultiPlan& mp = c.plan->multi;
     const PlanDeviceCopy* pd = c.pd;
-    const UniformLayout& ulo = c.ul;
     hipStream_t s = c.s;
     unsigned long long* counters = c.counters;
-    const int64_t A = (int64_t)c.plan->matchers.size(), cap = c.cap;
+    const int64_t A = (int64_t)c.plan->matchers.size(), cap = c.cap, n_reads = c.reads.n;
     const int64_t chunk = std::max<int64_t>(1, cap / A);
-    for (int64_t lo = 0; lo < c.n_reads; lo += chunk) {
-        const int64_t cnt = std::min(chunk, c.n_reads - lo);
+    for (int64_t lo = 0; lo < n_reads; lo += chunk) {
+        const int64_t cnt = std::min(chunk, n_reads - lo);
         HIP_TRY(hipMemsetAsync(counters, 0, WS_HEADER, s));
         {
             MultiFilterArgs f;
-            f.uniform_first = ulo.first; f.uniform_len = ulo.len;
+            fill_reads(f, c.reads);
+            f.first_read = lo; f.n_reads = cnt;
             f.hdr = pd->d_mhdr; f.dir = pd->d_mdir; f.entries = pd->d_mentries; f.bitmap = pd->d_mbitmap;
-            f.seqs = c.d_seqs; f.offsets = c.d_offsets; f.lens = c.d_lens;
-            f.first_read = lo; f.n_reads = cnt; f.max_read_len = CAH_MAX_READ_LEN;
-            f.work_counter = counters + 0; f.status = c.d_status;
+            f.work_counter = counters + 0; f.status = c.out.status;
             f.pairs = c.sc.pairs; f.pair_count = counters + WS_QCOUNT; f.pair_cap = cap;
             ProfScope ps(s, CAH_PROF_FILTER, cnt);
             HIP_TRY(launch_multi_filter(f, mp.hdr, pd->n_cus, s));
         }
         {
             ScanArgs sa;
-            sa.uniform_first = ulo.first; sa.uniform_len = ulo.len;
+            fill_reads(sa, c.reads);
+            fill_results(sa, c.out, 0, 1);
+            sa.n_reads = cnt * A;                                  // (the work list holds pairs)
             sa.matcher = pd->d_matchers;
-            sa.seqs = c.d_seqs; sa.offsets = c.d_offsets; sa.lens = c.d_lens; sa.n_reads = cnt * A;
-            sa.max_read_len = CAH_MAX_READ_LEN;
-            sa.queue = nullptr; sa.queue_count = counters + WS_QCOUNT; sa.queue_keys = nullptr;
+            sa.queue_count = counters + WS_QCOUNT;
             sa.work_counter = counters + WS_SCANWORK;
-            sa.out6 = c.d_out6; sa.status = c.d_status; sa.best_adapter = c.d_best_adapter;
-            sa.adapter_index = 0; sa.merge_best = 1;
             sa.pairs = c.sc.pairs; sa.tab = pd->d_mscan; sa.n_adapters = (int32_t)A; sa.multi_skip_ok = mp.hdr.skip_ok;
             sa.best_key = c.sc.best_key;
             sa.dp_queue = c.sc.dpq; sa.dp_win = c.sc.win;
             sa.dp_count_front = counters + WS_DPFRONT; sa.dp_count_back = counters + WS_DPBACK;
             sa.dp_cap = cap;
-            sa.retry_threshold = 0; sa.retry_queue = nullptr; sa.retry_keys = nullptr; sa.retry_count = nullptr;
-            sa.retry_cap = 0; sa.queue_limit = 0; sa.early_stop = 0; sa.tile = 0;
             sa.kind = scan_word_kind(c.plan->matchers[0].m);       // all adapters of the fused path have one shape
             ProfScope ps(s, CAH_PROF_SCAN, cnt);
             HIP_TRY(launch_back_scan(sa, cnt * A, pd->n_cus, s));
         }
         {
             DpArgs a;
-            a.uniform_first = ulo.first; a.uniform_len = ulo.len;
+            fill_reads(a, c.reads);
+            fill_results(a, c.out, 0, 1);
+            a.n_reads = cnt * A;
             a.matcher = pd->d_matchers;
-            a.seqs = c.d_seqs; a.offsets = c.d_offsets; a.lens = c.d_lens; a.n_reads = cnt * A;
-            a.max_read_len = CAH_MAX_READ_LEN;
-            a.queue = c.sc.dpq; a.queue_count = counters + WS_DPFRONT; a.queue_keys = nullptr;
+            a.queue = c.sc.dpq; a.queue_count = counters + WS_DPFRONT;
             a.work_counter = counters + WS_DPWORK;
-            a.out6 = c.d_out6; a.status = c.d_status; a.best_adapter = c.d_best_adapter;
-            a.adapter_index = 0; a.merge_best = 1;
             a.win = c.sc.win; a.queue_count_back = counters + WS_DPBACK; a.queue_cap = cap;
             a.pairs = c.sc.pairs; a.tab = pd->d_mrow; a.n_adapters = (int32_t)A; a.best_key = c.sc.best_key;
             ProfScope ps(s, CAH_PROF_DP, cnt);
             HIP_TRY(launch_dp(a, c.plan->matchers[0].m, true, true, cnt * A, pd->n_cus, s));
         }
     }
-    ProfScope ps(s, CAH_PROF_MERGE, c.n_reads);
-    HIP_TRY(launch_multi_decode(c.sc.best_key, c.n_reads, c.d_out6, c.d_status, c.d_best_adapter, pd->n_cus, s));
+    ProfScope ps(s, CAH_PROF_MERGE, n_reads);
+    HIP_TRY(launch_multi_decode(c.sc.best_key, n_reads, c.out.out6, c.out.status, c.out.best, pd->n_cus, s));
     return CAH_OK;
 }
 
 static int match_batch_multi_once(const MultiCall& c, int path) {
-    HIP_TRY(hipMemsetAsync(c.sc.best_key, 0, sizeof(unsigned long long) * (size_t)c.n_reads, c.s));
+    HIP_TRY(hipMemsetAsync(c.sc.best_key, 0, sizeof(unsigned long long) * (size_t)c.reads.n, c.s));
     return path == CAH_MULTI_STREAM ? run_multi_stream(c) : run_multi_fused(c);
 }
 // (a wave that gave up waiting for its tile -- err bit 1: nothing is wrong with the batch, the device was busy with
 // something else for seconds -- is no reason to fail the call: the batch is matched once more from the start)
 // route: the FUSED or STREAM route of this batch (multi_route.h); `extra` is the scratch behind the base workspace
-static int match_batch_multi(const cah_plan* plan, const PlanDeviceCopy* pd, const uint8_t* d_seqs,
-                             const int64_t* d_offsets, const int32_t* d_lens, int64_t n_reads, int32_t* d_out6,
-                             int32_t* d_best_adapter, uint8_t* d_status, const Workspace& ws, char* extra,
-                             hipStream_t s, const MultiRoute& route) {
-    const int64_t cap = multi_pair_cap(plan, n_reads);
-    const MultiCall c{plan, pd, d_seqs, d_offsets, d_lens, n_reads, d_out6, d_best_adapter, d_status, ws.counters, s, route.ul,
-                      cap, MultiScratch(extra, cap, n_reads)};
+static int match_batch_multi(const cah_plan* plan, const PlanDeviceCopy* pd, const Reads& reads, const Results& out,
+                             const Workspace& ws, char* extra, hipStream_t s, const MultiRoute& route) {
+    const int64_t cap = multi_pair_cap(plan, reads.n);
+    const MultiCall c{plan, pd, reads.with(route.ul), out, ws.counters, s, cap, MultiScratch(extra, cap, reads.n)};
     t_m2_waited_in_vain = false;
     int rc = match_batch_multi_once(c, route.path);
     if (rc == CAH_EINTERNAL && t_m2_waited_in_vain) {
@@ -1807,15 +1810,16 @@ static int match_batch_multi(const cah_plan* plan, const PlanDeviceCopy* pd, con
     return rc;
 }
 
-static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const int64_t* d_offsets,
-                            const int32_t* d_lens, const UniformLayout ul, int64_t n_reads, int32_t* d_out6,
-                            int32_t* d_best_adapter, uint8_t* d_status, void* d_workspace, size_t workspace_bytes,
-                            void* stream, const FrontFuse* fuse = nullptr, const CallHints* hints = nullptr) {
+static int match_batch_impl(const cah_plan* plan, const Reads& reads, const Results& out, void* d_workspace,
+                            size_t workspace_bytes, void* stream, const FrontFuse* fuse = nullptr,
+                            const CallHints* hints = nullptr) {
+    const UniformLayout& ul = reads.ul;
+    const int64_t n_reads = reads.n;
     const bool outputs_ready = hints && hints->outputs_ready;
-    int rc = check_batch(plan, d_seqs, (ul.len > 0 && !ul.suffix) ? (const void*)d_seqs : (const void*)d_offsets, n_reads);
+    int rc = check_batch(plan, reads.seqs, (ul.len > 0 && !ul.suffix) ? (const void*)reads.seqs : (const void*)reads.offsets, n_reads);
     if (rc) return rc;
     if (n_reads == 0) return CAH_OK;
-    if (!d_out6 || !d_status) return fail(CAH_EINVAL, "output pointers are NULL");
+    if (!out.out6 || !out.status) return fail(CAH_EINVAL, "output pointers are NULL");
     if (!d_workspace || workspace_bytes < cah_workspace_bytes(n_reads))
         return fail(CAH_EINVAL, "workspace too small: need %zu bytes", cah_workspace_bytes(n_reads));
     hipStream_t s = (hipStream_t)stream;
@@ -1826,12 +1830,12 @@ static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const i
     // streaming multi-adapter form has a use for a frame length (cah_match_batch_frames); the per-adapter loop below takes
     // the caller's layout (a single adapter's streaming prefilter decides adapter by adapter: run_filter)
     MultiBatch mb;
-    mb.ul = ul; mb.has_lens = d_lens != nullptr; mb.ws_fits = workspace_bytes >= cah_plan_workspace_bytes(plan, n_reads);
+    mb.ul = ul; mb.has_lens = reads.lens != nullptr; mb.ws_fits = workspace_bytes >= cah_plan_workspace_bytes(plan, n_reads);
     const MultiRoute route = multi_route(plan->multi, mb, plan->multi.form == M_NONE ? MultiSwitches() : multi_switches());
     const bool multi_path = route.path != CAH_MULTI_SEQUENTIAL;
     const Workspace ws(d_workspace, n_reads, workspace_bytes);
     unsigned long long* counters = ws.counters;
-    const UniformLayout ul_rest = ul.suffix ? UniformLayout() : ul;     // what every kernel but the prefilter sees
+    const Reads rest = reads.with(ul.suffix ? UniformLayout() : ul);    // what every kernel but the prefilter sees
     // The result rows are zeroed by the first adapter's prefilter on its way through the batch when there is one
     // (FilterArgs::clear_out6: 24 B per read that would otherwise be a memset pass of its own), by a memset if not.
     int32_t first_aligner = -1;
@@ -1842,10 +1846,10 @@ static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const i
                                runs_filter(plan->matchers[(size_t)first_aligner]) && n_reads > CAH_TINY_BATCH &&
                                !(env_flag("CAH_NO_FILTER_CLEAR") && !fuse);
     if (!outputs_ready) {
-        HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n_reads, s));
+        HIP_TRY(hipMemsetAsync(out.status, 0, (size_t)n_reads, s));
         // (the fused multi-adapter path's last kernel, k_multi_decode, writes every row, status and best adapter)
-        if (!filter_clears && !multi_path) HIP_TRY(hipMemsetAsync(d_out6, 0, sizeof(int32_t) * 6 * (size_t)n_reads, s));
-        if (d_best_adapter && !filter_clears && !multi_path) HIP_TRY(launch_init_best(d_best_adapter, n_reads, pd->n_cus, s));
+        if (!filter_clears && !multi_path) HIP_TRY(hipMemsetAsync(out.out6, 0, sizeof(int32_t) * 6 * (size_t)n_reads, s));
+        if (out.best && !filter_clears && !multi_path) HIP_TRY(launch_init_best(out.best, n_reads, pd->n_cus, s));
     }
     // tiny single-adapter batches: one memset for all counters, no batch check (the ragged prefilter serves them)
     const bool tiny = n_reads <= CAH_TINY_BATCH && plan->matchers.size() == 1;
@@ -1853,49 +1857,64 @@ static int match_batch_impl(const cah_plan* plan, const uint8_t* d_seqs, const i
     const bool header_fresh = tiny;
     // one pass over the offsets decides, on the device, which prefilter kernel works on this batch
     const unsigned long long* d_batch_flag = nullptr;
-    if (!d_lens && !tiny && ul.len == 0 && !ul.suffix) {
+    if (!reads.lens && !tiny && ul.len == 0 && !ul.suffix) {
         bool any_lean = false;
         for (size_t ad = 0; ad < plan->matchers.size(); ad++)
             any_lean |= runs_filter(plan->matchers[ad]) && plan->matchers[ad].kind != CAH_KIND_KMER_ONLY && plan->lean[ad].ok;
         if (any_lean) {
             HIP_TRY(hipMemsetAsync(counters + WS_UFLAG, 0, sizeof(unsigned long long), s));
-            HIP_TRY(launch_uniform_check(d_offsets, n_reads, CAH_MAX_READ_LEN, counters + WS_UFLAG, pd->n_cus, s));
+            HIP_TRY(launch_uniform_check(reads.offsets, n_reads, CAH_MAX_READ_LEN, counters + WS_UFLAG, pd->n_cus, s));
             d_batch_flag = counters + WS_UFLAG;
         }
     }
     t_last_multi_path = route.path;
     if (multi_path)
-        return match_batch_multi(plan, pd, d_seqs, d_offsets, d_lens, n_reads, d_out6, d_best_adapter, d_status, ws,
-                                 (char*)d_workspace + cah_workspace_bytes(n_reads), s, route);
+        return match_batch_multi(plan, pd, reads, out, ws, (char*)d_workspace + cah_workspace_bytes(n_reads), s, route);
+    const WorkList survivors{ws.queue, counters + WS_QCOUNT, ws.keys};
     for (int32_t ad = 0; ad < (int32_t)plan->matchers.size(); ad++) {
         const CahMatcher& mt = plan->matchers[(size_t)ad];
         if (mt.kind == CAH_KIND_KMER_ONLY) continue;
         if (runs_filter(mt)) {
             // prefilter -> queue of surviving reads -> (cost scan ->) DP on dense waves
-            rc = run_filter(plan, pd, ad, d_seqs, d_offsets, d_lens, n_reads, 1, nullptr, d_status, ws.queue,
-                            counters + WS_QCOUNT, ws.keys, counters + 0, d_batch_flag, s,
-                            (filter_clears && ad == first_aligner) ? d_out6 : nullptr,
-                            (filter_clears && ad == first_aligner) ? d_best_adapter : nullptr, ul,
-                            ad == first_aligner ? fuse : nullptr, header_fresh);
+            FilterOpts fo;
+            if (filter_clears && ad == first_aligner) fo.clear = out;
+            if (ad == first_aligner) fo.fuse = fuse;
+            fo.header_fresh = header_fresh;
+            rc = run_filter(plan, pd, ad, reads, 1, nullptr, out.status, survivors, counters + 0, d_batch_flag, s, fo);
             if (rc) return rc;
             // merge mode 2: the plan's first adapter writes into zeroed rows -- nothing to compare with (kernels.hip,
             // store_result)
-            rc = run_aligner(plan, pd, ad, d_seqs, d_offsets, d_lens, n_reads, ws.queue, counters + WS_QCOUNT,
-                             ws.keys, ws, d_out6, d_status, d_best_adapter, ad == first_aligner ? 2 : 1, s, ul_rest,
-                             header_fresh);
+            rc = run_aligner(plan, pd, ad, rest, survivors, ws, out, ad == first_aligner ? 2 : 1, s, header_fresh);
         } else {
-            rc = run_aligner(plan, pd, ad, d_seqs, d_offsets, d_lens, n_reads, nullptr, nullptr, nullptr,
-                             ws, d_out6, d_status, d_best_adapter, 1, s, ul_rest, header_fresh);
+            rc = run_aligner(plan, pd, ad, rest, WorkList(), ws, out, 1, s, header_fresh);
         }
         if (rc) return rc;
     }
     return CAH_OK;
 }
 
+// The public forms of a batch differ in what the host knows about its layout (multi_route.h: UniformLayout): a length
+// argument that is checked, and the flags that go with it.
+static int check_len(const char* what, int32_t len) {
+    if (len < 1 || len > CAH_MAX_READ_LEN) return fail(CAH_EINVAL, "%s out of range (1..%d)", what, CAH_MAX_READ_LEN);
+    return CAH_OK;
+}
+static UniformLayout layout_of(int32_t len, bool suffix = false, bool inner = false, bool general = false) {
+    return UniformLayout{0, len, suffix, inner, general};
+}
+// views (starts + lengths) with a parent or frame length `len`, named `what` in the caller's signature
+static int match_batch_views(const cah_plan* plan, const uint8_t* d_seqs, const int64_t* d_starts, const int32_t* d_lens,
+                             const char* what, const UniformLayout& ul, int64_t n_reads, const Results& out,
+                             void* d_workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_len(what, ul.len)) return rc;
+    if (n_reads > 0 && (!d_starts || !d_lens)) return fail(CAH_EINVAL, "starts / lens are NULL");
+    return match_batch_impl(plan, Reads{d_seqs, d_starts, d_lens, n_reads, ul}, out, d_workspace, workspace_bytes, stream);
+}
+
 int cah_match_batch(const cah_plan* plan, const uint8_t* d_seqs, const int64_t* d_offsets,
                     const int32_t* d_lens, int64_t n_reads, int32_t* d_out6, int32_t* d_best_adapter,
                     uint8_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
-    return match_batch_impl(plan, d_seqs, d_offsets, d_lens, UniformLayout(), n_reads, d_out6, d_best_adapter, d_status,
+    return match_batch_impl(plan, Reads{d_seqs, d_offsets, d_lens, n_reads}, Results{d_out6, d_status, d_best_adapter},
                             d_workspace, workspace_bytes, stream);
 }
 
@@ -1906,13 +1925,10 @@ int cah_match_batch(const cah_plan* plan, const uint8_t* d_seqs, const int64_t* 
 int cah_match_batch_uniform(const cah_plan* plan, const uint8_t* d_seqs, int32_t read_len, int64_t n_reads,
                             int32_t* d_out6, int32_t* d_best_adapter, uint8_t* d_status, void* d_workspace,
                             size_t workspace_bytes, void* stream) {
-    if (read_len < 1 || read_len > CAH_MAX_READ_LEN)
-        return fail(CAH_EINVAL, "read_len out of range (1..%d)", CAH_MAX_READ_LEN);
+    if (int rc = check_len("read_len", read_len)) return rc;
     if (n_reads > 0 && !d_seqs) return fail(CAH_EINVAL, "seqs is NULL");
-    UniformLayout ul;
-    ul.first = 0; ul.len = read_len;
-    return match_batch_impl(plan, d_seqs, nullptr, nullptr, ul, n_reads, d_out6, d_best_adapter, d_status, d_workspace,
-                            workspace_bytes, stream);
+    return match_batch_impl(plan, Reads{d_seqs, nullptr, nullptr, n_reads, layout_of(read_len)},
+                            Results{d_out6, d_status, d_best_adapter}, d_workspace, workspace_bytes, stream);
 }
 
 // Views that are SUFFIXES of the reads of a uniform batch: view r = d_seqs[d_starts[r], d_starts[r] + d_lens[r]) with
@@ -1925,13 +1941,8 @@ int cah_match_batch_suffix_views(const cah_plan* plan, const uint8_t* d_seqs, co
                                  const int32_t* d_lens, int32_t parent_read_len, int64_t n_reads, int32_t* d_out6,
                                  int32_t* d_best_adapter, uint8_t* d_status, void* d_workspace, size_t workspace_bytes,
                                  void* stream) {
-    if (parent_read_len < 1 || parent_read_len > CAH_MAX_READ_LEN)
-        return fail(CAH_EINVAL, "parent_read_len out of range (1..%d)", CAH_MAX_READ_LEN);
-    if (n_reads > 0 && (!d_starts || !d_lens)) return fail(CAH_EINVAL, "starts / lens are NULL");
-    UniformLayout ul;
-    ul.first = 0; ul.len = parent_read_len; ul.suffix = true;
-    return match_batch_impl(plan, d_seqs, d_starts, d_lens, ul, n_reads, d_out6, d_best_adapter, d_status, d_workspace,
-                            workspace_bytes, stream);
+    return match_batch_views(plan, d_seqs, d_starts, d_lens, "parent_read_len", layout_of(parent_read_len, true), n_reads,
+                             Results{d_out6, d_status, d_best_adapter}, d_workspace, workspace_bytes, stream);
 }
 
 // Views ANYWHERE inside the reads of a uniform batch: view r = d_seqs[d_starts[r], d_starts[r] + d_lens[r]) with
@@ -1943,13 +1954,8 @@ int cah_match_batch_suffix_views(const cah_plan* plan, const uint8_t* d_seqs, co
 int cah_match_batch_views(const cah_plan* plan, const uint8_t* d_seqs, const int64_t* d_starts, const int32_t* d_lens,
                           int32_t parent_read_len, int64_t n_reads, int32_t* d_out6, int32_t* d_best_adapter,
                           uint8_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (parent_read_len < 1 || parent_read_len > CAH_MAX_READ_LEN)
-        return fail(CAH_EINVAL, "parent_read_len out of range (1..%d)", CAH_MAX_READ_LEN);
-    if (n_reads > 0 && (!d_starts || !d_lens)) return fail(CAH_EINVAL, "starts / lens are NULL");
-    UniformLayout ul;
-    ul.first = 0; ul.len = parent_read_len; ul.suffix = true; ul.inner = true;
-    return match_batch_impl(plan, d_seqs, d_starts, d_lens, ul, n_reads, d_out6, d_best_adapter, d_status, d_workspace,
-                            workspace_bytes, stream);
+    return match_batch_views(plan, d_seqs, d_starts, d_lens, "parent_read_len", layout_of(parent_read_len, true, true), n_reads,
+                             Results{d_out6, d_status, d_best_adapter}, d_workspace, workspace_bytes, stream);
 }
 
 // Views ANYWHERE in d_seqs, none longer than frame_len characters: a packed batch with its offsets (d_starts[r] =
@@ -1960,13 +1966,8 @@ int cah_match_batch_views(const cah_plan* plan, const uint8_t* d_seqs, const int
 int cah_match_batch_frames(const cah_plan* plan, const uint8_t* d_seqs, const int64_t* d_starts, const int32_t* d_lens,
                            int32_t frame_len, int64_t n_reads, int32_t* d_out6, int32_t* d_best_adapter,
                            uint8_t* d_status, void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (frame_len < 1 || frame_len > CAH_MAX_READ_LEN)
-        return fail(CAH_EINVAL, "frame_len out of range (1..%d)", CAH_MAX_READ_LEN);
-    if (n_reads > 0 && (!d_starts || !d_lens)) return fail(CAH_EINVAL, "starts / lens are NULL");
-    UniformLayout ul;
-    ul.first = 0; ul.len = frame_len; ul.suffix = true; ul.inner = true; ul.general = true;
-    return match_batch_impl(plan, d_seqs, d_starts, d_lens, ul, n_reads, d_out6, d_best_adapter, d_status, d_workspace,
-                            workspace_bytes, stream);
+    return match_batch_views(plan, d_seqs, d_starts, d_lens, "frame_len", layout_of(frame_len, true, true, true), n_reads,
+                             Results{d_out6, d_status, d_best_adapter}, d_workspace, workspace_bytes, stream);
 }
 
 extern "C" int cah_linked_views(const int32_t*, const uint8_t*, const int64_t*, const int32_t*, int32_t, int64_t, int64_t*,
@@ -1999,34 +2000,34 @@ int cah_linked_match_batch_uniform(const cah_plan* front_plan, const cah_plan* b
                                    uint8_t* d_status_back, int64_t* d_starts, int32_t* d_view_lens, void* d_workspace,
                                    size_t workspace_bytes, void* stream) {
     if (!front_plan || !back_plan) return fail(CAH_EINVAL, "plan is NULL");
-    if (read_len < 1 || read_len > CAH_MAX_READ_LEN)
-        return fail(CAH_EINVAL, "read_len out of range (1..%d)", CAH_MAX_READ_LEN);
+    if (int rc = check_len("read_len", read_len)) return rc;
     if (n_reads < 0 || n_reads > 2147483647LL) return fail(CAH_EINVAL, "n_reads out of range (0..2^31-1)");
     if (n_reads == 0) return CAH_OK;
     if (!d_seqs || !d_out6_front || !d_status_front || !d_out6_back || !d_status_back || !d_starts || !d_view_lens)
         return fail(CAH_EINVAL, "cah_linked_match_batch_uniform: NULL argument");
-    UniformLayout views;
-    views.first = 0; views.len = read_len; views.suffix = true;
+    const Reads views{d_seqs, d_starts, d_view_lens, n_reads, layout_of(read_len, true)};
+    const Results front{d_out6_front, d_status_front, d_best_front}, back{d_out6_back, d_status_back, d_best_back};
     if (linked_fusable(front_plan, back_plan, read_len, n_reads)) {
         const PlanDeviceCopy* fpd = nullptr;
         int rc = plan_on_device(front_plan, &fpd);
         if (rc) return rc;
-        FrontFuse fuse;
-        fuse.d_matcher = fpd->d_matchers;
-        fuse.out6 = d_out6_front; fuse.status = d_status_front; fuse.best = d_best_front;
-        fuse.starts = d_starts; fuse.lens = d_view_lens;
-        return match_batch_impl(back_plan, d_seqs, d_starts, d_view_lens, views, n_reads, d_out6_back, d_best_back,
-                                d_status_back, d_workspace, workspace_bytes, stream, &fuse);
+        const FrontFuse fuse{fpd->d_matchers, front, d_starts, d_view_lens};
+        return match_batch_impl(back_plan, views, back, d_workspace, workspace_bytes, stream, &fuse);
     }
-    UniformLayout ul;
-    ul.first = 0; ul.len = read_len;
-    int rc = match_batch_impl(front_plan, d_seqs, nullptr, nullptr, ul, n_reads, d_out6_front, d_best_front, d_status_front,
-                              d_workspace, workspace_bytes, stream);
+    int rc = match_batch_impl(front_plan, Reads{d_seqs, nullptr, nullptr, n_reads, layout_of(read_len)}, front, d_workspace,
+                              workspace_bytes, stream);
     if (rc) return rc;
     rc = cah_linked_views(d_out6_front, d_status_front, nullptr, nullptr, read_len, n_reads, d_starts, d_view_lens, stream);
     if (rc) return rc;
-    return match_batch_impl(back_plan, d_seqs, d_starts, d_view_lens, views, n_reads, d_out6_back, d_best_back,
-                            d_status_back, d_workspace, workspace_bytes, stream);
+    return match_batch_impl(back_plan, views, back, d_workspace, workspace_bytes, stream);
+}
+
+// the current device's compute units (256 where it cannot be asked): sizes the grid of kernels that run without a plan
+static int device_cus() {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) return v;
+    return 256;
 }
 
 int cah_validate_ascii_batch(const uint8_t* d_seqs, const int64_t* d_offsets, const int32_t* d_lens,
@@ -2036,12 +2037,7 @@ int cah_validate_ascii_batch(const uint8_t* d_seqs, const int64_t* d_offsets, co
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(d_bad, 0, sizeof(int32_t), s));
     if (n_reads <= 0) return CAH_OK;
-    int dev = 0, n_cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n_cus = v;
-    }
-    HIP_TRY(launch_validate(d_seqs, d_offsets, d_lens, n_reads, d_bad, n_cus, s));
+    HIP_TRY(launch_validate(d_seqs, d_offsets, d_lens, n_reads, d_bad, device_cus(), s));
     return CAH_OK;
 }
 
@@ -2126,6 +2122,7 @@ static int host_call_one(int mode, const cah_plan* plan, const uint8_t* seq, int
     int32_t* d_best = (int32_t*)(d_pin + in_bytes + 24);
     uint8_t* d_status = (uint8_t*)(d_pin + in_bytes + 28);
     char* d_ws = hs.dev;                                         // always the same place: the marker below stays valid
+    const Reads one{d_seqs, d_offsets, nullptr, 1};
     // One 3' aligner with the cost scan (every plain -a adapter): prefilter + scan in ONE single-wave launch
     // (k_tiny); only a read the scan cannot finish costs a second launch (the cell DP over the list k_tiny left).
     const CahMatcher& mt0 = plan->matchers[0];
@@ -2141,7 +2138,7 @@ static int host_call_one(int mode, const cah_plan* plan, const uint8_t* seq, int
         const bool filter = mode == HOST_MATCH && mt0.has_filter;
         ta.lean = filter ? pd->d_lean : nullptr;
         ta.matcher = pd->d_matchers;
-        ta.seqs = d_seqs; ta.offsets = d_offsets; ta.n_reads = 1; ta.max_read_len = CAH_MAX_READ_LEN;
+        ta.seqs = one.seqs; ta.offsets = one.offsets; ta.n_reads = one.n; ta.max_read_len = CAH_MAX_READ_LEN;
         ta.out6 = d_out6; ta.status = d_status;
         ta.dp_queue = ws.dp_queue; ta.dp_win = ws.dp_win;
         ta.dp_count_front = ws.counters + WS_DPFRONT; ta.dp_count_back = ws.counters + WS_DPBACK;
@@ -2178,24 +2175,23 @@ static int host_call_one(int mode, const cah_plan* plan, const uint8_t* seq, int
                 void* fresh = nullptr;
                 HIP_TRY(hipMalloc(&fresh, CAH_TINY_IMAGE_BYTES));
                 TinyArgs tb = ta;
-                tb.image = nullptr; tb.image_out = fresh;
+                tb.image_out = fresh;
                 HIP_TRY(launch_tiny(tb, filter ? lf.n_lead : 1, filter ? lf.n_gated : 1, filter ? lf.lead_delay : 0, hs.stream));
                 HIP_TRY(hipStreamSynchronize(hs.stream));
                 img = fresh;
             }
-            ta.image = img; ta.image_out = nullptr;
+            ta.image = img;
         }
         HIP_TRY(launch_tiny(ta, filter ? lf.n_lead : 1, filter ? lf.n_gated : 1, filter ? lf.lead_delay : 0, hs.stream));
         if ((rc = wait_ticket(t_ticket))) return rc;
         if (*h_need > 0) {
             DpArgs a;
+            fill_reads(a, one);
+            fill_results(a, Results{d_out6, d_status}, 0, 0);
             a.matcher = pd->d_matchers;
-            a.seqs = d_seqs; a.offsets = d_offsets; a.lens = nullptr; a.n_reads = 1; a.max_read_len = CAH_MAX_READ_LEN;
-            a.queue = ws.dp_queue; a.queue_keys = nullptr; a.win = ws.dp_win;
+            a.queue = ws.dp_queue; a.win = ws.dp_win;
             a.queue_count = ws.counters + WS_DPFRONT; a.queue_count_back = ws.counters + WS_DPBACK; a.queue_cap = 1;
             a.work_counter = ws.counters + WS_DPWORK;
-            a.out6 = d_out6; a.status = d_status; a.best_adapter = nullptr; a.adapter_index = 0; a.merge_best = 0;
-            a.pairs = nullptr; a.tab = nullptr; a.n_adapters = 0; a.best_key = nullptr;
             HIP_TRY(launch_dp(a, mt0.m, mt0.indel_cost == 1, mt0.flags == 14, 1, pd->n_cus, hs.stream));
             t_ticket += 1;
             HIP_TRY(launch_ticket(d_done, t_ticket, hs.stream));
@@ -2212,8 +2208,7 @@ static int host_call_one(int mode, const cah_plan* plan, const uint8_t* seq, int
         CallHints hints;
         hints.outputs_ready = true;                              // (h_out was zeroed above: the outputs live in mapped host memory)
         hints.precleaned_ws = hs.precleaned_ws;
-        rc = match_batch_impl(plan, d_seqs, d_offsets, nullptr, UniformLayout(), 1, d_out6, d_best, d_status, d_ws, ws_bytes,
-                              hs.stream, nullptr, &hints);
+        rc = match_batch_impl(plan, one, Results{d_out6, d_status, d_best}, d_ws, ws_bytes, hs.stream, nullptr, &hints);
         // the next call's counters (tiny path of the batch entry), off its critical path
         if (rc == CAH_OK && hipMemsetAsync(d_ws, 0, WS_HEADER, hs.stream) == hipSuccess) hs.precleaned_ws = d_ws;
         else hs.precleaned_ws = nullptr;
@@ -2268,7 +2263,7 @@ static int host_call(int mode, const cah_plan* plan, int32_t adapter, const uint
         HIP_TRY(hipMemsetAsync(d_out, 0, o6_bytes + best_bytes + (size_t)n, hs.stream));
         CallHints hints;
         hints.outputs_ready = true;
-        rc = match_batch_impl(plan, d_seqs, d_offsets, nullptr, UniformLayout(), n, d_out6, d_best, d_status, d_ws, ws_bytes,
+        rc = match_batch_impl(plan, Reads{d_seqs, d_offsets, nullptr, n}, Results{d_out6, d_status, d_best}, d_ws, ws_bytes,
                               hs.stream, nullptr, &hints);
     }
     if (rc) return rc;
@@ -2290,9 +2285,7 @@ static int host_call(int mode, const cah_plan* plan, int32_t adapter, const uint
 
 int cah_locate_batch_host(const cah_plan* plan, int32_t adapter, const uint8_t* seqs,
                           const int64_t* offsets, int64_t n_reads, int32_t* out6, uint8_t* status) {
-    int rc = check_batch(plan, seqs, offsets, n_reads);
-    if (rc) return rc;
-    rc = check_adapter(plan, adapter);
+    int rc = check_batch(plan, adapter, seqs, offsets, n_reads);
     if (rc) return rc;
     if (n_reads == 0) return CAH_OK;
     if (!out6 || !status) return fail(CAH_EINVAL, "output pointers are NULL");
@@ -2301,9 +2294,7 @@ int cah_locate_batch_host(const cah_plan* plan, int32_t adapter, const uint8_t* 
 
 int cah_kmers_present_batch_host(const cah_plan* plan, int32_t adapter, const uint8_t* seqs,
                                  const int64_t* offsets, int64_t n_reads, uint8_t* present) {
-    int rc = check_batch(plan, seqs, offsets, n_reads);
-    if (rc) return rc;
-    rc = check_adapter(plan, adapter);
+    int rc = check_batch(plan, adapter, seqs, offsets, n_reads);
     if (rc) return rc;
     if (n_reads == 0) return CAH_OK;
     if (!present) return fail(CAH_EINVAL, "present is NULL");
@@ -2385,13 +2376,11 @@ int cah_locate_debug_host(const cah_adapter_desc* adapter, const uint8_t* seq, i
         HIP_TRY(hipMemcpy(b.p[8], cost_matrix, sizeof(int32_t) * cells, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(b.p[9], score_matrix, sizeof(int32_t) * cells, hipMemcpyHostToDevice));
         LongArgs la;
+        fill_reads(la, Reads{(const uint8_t*)b.p[3], (const int64_t*)b.p[4], nullptr, 1});
+        fill_results(la, Results{(int32_t*)b.p[7], (uint8_t*)b.p[7] + 6 * sizeof(int32_t)}, 0, 0);
         la.lm = (const CahLongMatcher*)b.p[0]; la.ref = (const uint8_t*)b.p[1]; la.ncnt = (const int32_t*)b.p[2];
-        la.seqs = (const uint8_t*)b.p[3]; la.offsets = (const int64_t*)b.p[4]; la.lens = nullptr;
-        la.n_reads = 1; la.max_read_len = CAH_MAX_READ_LEN;
-        la.queue = nullptr; la.queue_count = nullptr; la.work_counter = (unsigned long long*)b.p[5];
+        la.work_counter = (unsigned long long*)b.p[5];
         la.scratch = (int32_t*)b.p[6];
-        la.out6 = (int32_t*)b.p[7]; la.status = (uint8_t*)b.p[7] + 6 * sizeof(int32_t);
-        la.best_adapter = nullptr; la.adapter_index = 0; la.merge_best = 0;
         la.dbg_cost = (int32_t*)b.p[8]; la.dbg_score = (int32_t*)b.p[9];
         HIP_TRY(launch_dp_long(la, lanes, nullptr));
         HIP_TRY(hipDeviceSynchronize());
@@ -2427,13 +2416,8 @@ int cah_synth_reads(uint64_t seed, int64_t first_index, int64_t n_reads, int32_t
     int32_t zero = 0;
     HIP_TRY(hipMemcpyAsync(d_off.p, n_adapters > 0 ? adapter_off : &zero, sizeof(int32_t) * (size_t)(n_adapters + 1),
                            hipMemcpyHostToDevice, s));
-    int dev = 0, n_cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n_cus = v;
-    }
     HIP_TRY(launch_synth(seed, first_index, n_reads, read_len, p_adapter_u32, p_edit_u32, p_n_u16,
-                         (const char*)d_ad.p, (const int32_t*)d_off.p, n_adapters, d_seqs, d_offsets, n_cus, s));
+                         (const char*)d_ad.p, (const int32_t*)d_off.p, n_adapters, d_seqs, d_offsets, device_cus(), s));
     HIP_TRY(hipStreamSynchronize(s));   // d_ad/d_off are freed on return
     return CAH_OK;
 }

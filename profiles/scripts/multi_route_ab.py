@@ -6,7 +6,8 @@ and the other build against itself for the spread of the box.
 One driver process starts worker processes in turn -- other, this, other again -- `--rounds` times (a process loads one
 library; CAH_LIB_PATH selects it).  Every worker times the same workloads with host clocks around calls that end in a
 device synchronise: C4 (96 adapters, uniform reads), C4's reads as a ragged packed batch (frames), 384 33-mers (groups of
-tables) and the small batches of a length bucket, down to 10 000 reads, where the host's work per call shows.  A workload's
+tables) and the small batches of a length bucket, down to 10 000 reads, where the host's work per call shows, and the per-read calls
+(cah_match_one_host / cah_locate_one_host on one read of 150 characters: all host work and launch latency).  A workload's
 figure is the median call of a worker; `this_over_other` compares the medians over the rounds, `other_again_over_other` is
 the same figure for two sets of runs of ONE library, and `band` the range of the other library's single workers around
 their median: this library is no slower where its ratio lies inside what the other library does against itself."""
@@ -72,6 +73,18 @@ def worker():
     plan = plan_of(seqs)
     batch = ReadBatch.synthetic(5_000_000, 150, seqs, seed=5, p_adapter=0.4, p_edit=0.04, p_n=0.01)
     out["384 x 33 grouped 5M"] = calls_ms(plan, batch, 5, "stream")
+    del batch
+    # the per-read calls: one adapter, one read (a 3' adapter inside it: prefilter, scan and the tuple)
+    L = _lib.lib()
+    plan = plan_of([c4[0]])
+    read = "".join(prng.choice("ACGT") for _ in range(110)) + c4[0][:40]
+    for name, fn in (("match_one_host 150", L.cah_match_one_host), ("locate_one_host 150", L.cah_locate_one_host)):
+        ms = []
+        for i in range(3200):
+            t0 = time.perf_counter()
+            _lib.one_read(fn, plan.handle, read)
+            ms.append(1e3 * (time.perf_counter() - t0))
+        out[name] = statistics.median(ms[200:])
     print(json.dumps({"build_id": _lib.build_id(), "ms": out}), flush=True)
 
 
@@ -113,7 +126,7 @@ def main():
         row["inside_band"] = row["this_over_other"] <= row["band"][1]
         rows[w] = row
     doc = {"this_build_id": runs["this"][0]["build_id"], "other_build_id": runs["other"][0]["build_id"], "rounds": a.rounds,
-           "unit": "ms per call, median of a worker's calls (host clock, the call ends in a device synchronise)", "workloads": rows}
+           "unit": "ms per call, median of a worker's calls (host clock, the call ends in a device synchronise or the one-read calls' wait)", "workloads": rows}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(doc, fh, indent=1)
