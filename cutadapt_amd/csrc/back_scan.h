@@ -127,10 +127,15 @@ struct BackScanBook {
     // SUBS_FULL: cmin / je: smallest acceptable row-m cost so far and the first column that reached it;
     // eclean: that column's diagonal was clean (see A below).
     int cmin, je;
-    bool eclean;
-    bool edel;        // ONE_INDEL: the lowest unclean cell of that diagonal was reached from the cell above (a deletion)
-    bool epred_unclean;   // ... and the diagonal of the cell it was reached from is not clean either (or not tracked)
-    bool emore;       // a later column reached cmin again
+    // What else is known of column je, as bits of ONE word (BS_E_*): four bools were four lane masks in scalar register
+    // pairs through k_back_scan's column loop, merged with three scalar instructions apiece behind every guarded column.
+    unsigned eflags;
+};
+enum {
+    BS_E_CLEAN = 1,          // eclean
+    BS_E_DEL = 2,            // ONE_INDEL: the lowest unclean cell of that diagonal was reached from the cell above (a deletion)
+    BS_E_PRED_UNCLEAN = 4,   // ... and the diagonal of the cell it was reached from is not clean either (or not tracked)
+    BS_E_MORE = 8            // a later column reached cmin again
 };
 
 struct BackScanState : BackScanBook {
@@ -203,24 +208,21 @@ CAH_HD void bs_init(BackScanState& s, const BackScanParams& p) {
     s.VN = 0;
     s.cm = p.m;
     s.jfa = -1; s.jla = -1;
-    s.A = 0; s.cmin = 1 << 20; s.je = -1; s.eclean = false; s.edel = false; s.epred_unclean = true; s.emore = false;
+    s.A = 0; s.cmin = 1 << 20; s.je = -1; s.eflags = BS_E_PRED_UNCLEAN;
 }
 
-// Row m of the column just processed: the bookkeeping every representation shares.  clean: the diagonal that ends
-// in (m, j) has met no cell whose diagonal delta is 0 although its characters differ.  Returns true when the read
-// is finished as EXACT_FULL at this column.
+// Row m of the column just processed: the bookkeeping every representation shares.  eflags: BS_E_CLEAN -- the diagonal
+// that ends in (m, j) has met no cell whose diagonal delta is 0 although its characters differ -- and BS_E_DEL /
+// BS_E_PRED_UNCLEAN of that diagonal.  Returns true when the read is finished as EXACT_FULL at this column.
 // jlim: columns behind it are not booked (for callers whose window runs a few columns past the last one they answer for;
 // round 5's k_back_scan3 was one -- removed in round 6, DESIGN_HISTORY.md).
 template <bool SUBS>
-CAH_HD bool bs_book(BackScanBook& s, const bool clean, const int j, const BackScanParams& p, const bool del = false,
-                    const bool pred_unclean = true, const int jlim = 0x7FFFFFFF) {
+CAH_HD bool bs_book(BackScanBook& s, const unsigned eflags, const int j, const BackScanParams& p, const int jlim = 0x7FFFFFFF) {
     if (s.cm <= p.kacc && j <= jlim) {
         if (s.jfa < 0) s.jfa = j;
         s.jla = j;
-        if (SUBS && s.cm == s.cmin) s.emore = true;
-        if (SUBS && s.cm < s.cmin) {
-            s.cmin = s.cm; s.je = j; s.eclean = clean; s.edel = del; s.epred_unclean = pred_unclean; s.emore = false;
-        }
+        if (SUBS && s.cm == s.cmin) s.eflags |= BS_E_MORE;
+        if (SUBS && s.cm < s.cmin) { s.cmin = s.cm; s.je = j; s.eflags = eflags; }
         // (:521-533) a cost-0 candidate has score m, more than any earlier best (those cost >= 1: the
         // first cost-0 column ends the loop), so it replaces the best iff it is the first or
         // origin = j - m <= best.origin + m/2.  Every earlier acceptable candidate sits at a column
@@ -237,8 +239,11 @@ CAH_HD bool bs_book(BackScanBook& s, const bool clean, const int j, const BackSc
 // BOOK = false: the recurrence alone -- for windows in which no column but the last can hold an acceptable candidate
 // (the tail pairs of the streaming multi-adapter path, multi2.h): row m's cost is not followed, nothing is booked, the
 // rows of the last column are read off the state by bs_finish as ever (jfa stays -1).
+// exact_col (k_back_scan): where the FIRST column that finishes the read as EXACT_FULL is noted (-1 until then), inside the
+// rare booking branch.  A caller that keeps it there and ignores the returned bool carries no predicate from column to
+// column: a bool is a lane mask in a scalar register pair, merged behind every column's branch.
 template <bool SUBS = true, bool BOOK = true>
-CAH_HD bool bs_step(BackScanState& s, const uint64_t eq, const int j, const BackScanParams& p) {
+CAH_HD bool bs_step(BackScanState& s, const uint64_t eq, const int j, const BackScanParams& p, int* const exact_col = nullptr) {
     const uint64_t VP = s.VP, VN = s.VN;
     const uint64_t Xv = eq | VN;
     const uint64_t Xh = (((eq & VP) + VP) ^ VP) | eq;
@@ -252,7 +257,11 @@ CAH_HD bool bs_step(BackScanState& s, const uint64_t eq, const int j, const Back
     if (!BOOK) return false;
     // D0 = Xh | VN: C(i, j) == C(i-1, j-1); set where the characters differ = an indel path is as cheap
     if (SUBS) s.A = bs_shl1(s.A) | ((Xh | VN) & ~eq);
-    if (__builtin_expect(s.cm <= p.kacc, 0)) return bs_book<SUBS>(s, (s.A >> 63) == 0, j, p);     // rare: off the straight path
+    if (__builtin_expect(s.cm <= p.kacc, 0)) {                  // rare: off the straight path
+        const bool hit = bs_book<SUBS>(s, (unsigned)(~s.A >> 63) | BS_E_PRED_UNCLEAN, j, p);
+        if (exact_col != nullptr && hit && *exact_col < 0) *exact_col = j;
+        return hit;
+    }
     return false;
 }
 
@@ -277,7 +286,7 @@ CAH_HD void bs32_init(BackScanState32<X>& s, const BackScanParams& p) {
     for (int t = 0; t < (X > 0 ? X : 1); ++t) s.cx[t] = 1 + t;
     s.cm = p.m;
     s.jfa = -1; s.jla = -1;
-    s.cmin = 1 << 20; s.je = -1; s.eclean = false; s.edel = false; s.epred_unclean = true; s.emore = false;
+    s.cmin = 1 << 20; s.je = -1; s.eflags = BS_E_PRED_UNCLEAN;
     s.Z = 0; s.U = 0;
 }
 
@@ -285,7 +294,7 @@ template <bool SUBS, int X, bool BOOK = true>
 // (joff: added to j only where the column number is needed -- the booking of an acceptable column, off the straight path;
 // a kernel that unrolls sixteen columns passes its chunk's first column and the constants 1..16 instead of counting)
 CAH_HD bool bs32_step(BackScanState32<X>& s, const uint32_t eq, const uint32_t eqx, const int j, const BackScanParams& p,
-                      const int jlim = 0x7FFFFFFF, const int joff = 0) {
+                      const int jlim = 0x7FFFFFFF, const int joff = 0, int* const exact_col = nullptr) {
     // ---- the explicit rows 1..X and what they hand to the word: hin, and the bits that enter its diagonals
     uint32_t hpos = 0, hneg = 0, a_in = 0, u_in = 0, z_in = 0, a_top_new = 0;
     if (X == 1) {
@@ -346,8 +355,13 @@ CAH_HD bool bs32_step(BackScanState32<X>& s, const uint32_t eq, const uint32_t e
         const uint32_t pa = bs_sel(s.VP, X > 1 ? (bs_dbl(s.A) | a_top_new) : bs_dbl(s.A), a_old);
         s.Z = bs_sel(Xc, pa, X > 1 ? (bs_dbl(s.Z) | z_in) : bs_dbl(s.Z));
     }
-    if (__builtin_expect(s.cm <= p.kacc, 0))
-        return bs_book<SUBS>(s, (s.A >> 31) == 0, j + joff, p, (s.U >> 31) != 0, (s.Z >> 31) != 0, jlim);
+    if (__builtin_expect(s.cm <= p.kacc, 0)) {
+        // BS_E_CLEAN | BS_E_DEL | BS_E_PRED_UNCLEAN from the top bits of A, U and Z
+        const unsigned eflags = (~s.A >> 31) | ((s.U >> 31) << 1) | ((s.Z >> 31) << 2);
+        const bool hit = bs_book<SUBS>(s, eflags, j + joff, p, jlim);
+        if (exact_col != nullptr && hit && *exact_col < 0) *exact_col = j + joff;   // (see bs_step)
+        return hit;
+    }
     return false;
 }
 
@@ -469,16 +483,18 @@ CAH_HD int bs_finish_rows(const BackScanBook& s, const BsLastColumn<W, X>& col, 
     // the cell DP's first column is never before dp_lo: the scan's own window start, unless the caller knows an earlier
     // column that is as safe
     const int dp_lo = dp_lo_in >= 0 ? dp_lo_in : j0;
+    const bool eclean = (s.eflags & BS_E_CLEAN) != 0, edel = (s.eflags & BS_E_DEL) != 0;
+    const bool epred_unclean = (s.eflags & BS_E_PRED_UNCLEAN) != 0, emore = (s.eflags & BS_E_MORE) != 0;
     // one insertion / one deletion (see the header); INDEL1 = false: the form does not keep the bits
-    const bool indel1 = INDEL1 && s.cmin >= 1 && !s.eclean && !s.epred_unclean && s.je - p.m - 1 >= j0 &&
-                        s.je + 1 - s.jfa <= p.half_m - p.kacc && !(s.edel && s.emore);
-    const int indel1_score = p.m - 2 * s.cmin - (s.edel ? 1 : 0);
+    const bool indel1 = INDEL1 && s.cmin >= 1 && !eclean && !epred_unclean && s.je - p.m - 1 >= j0 &&
+                        s.je + 1 - s.jfa <= p.half_m - p.kacc && !(edel && emore);
+    const int indel1_score = p.m - 2 * s.cmin - (edel ? 1 : 0);
     if (stopped) {                   // jfa >= 0
-        if (s.cmin >= 1 && s.eclean && s.je - p.m >= j0 && s.je - s.jfa <= p.half_m - p.kacc) {
+        if (s.cmin >= 1 && eclean && s.je - p.m >= j0 && s.je - s.jfa <= p.half_m - p.kacc) {
             o0 = s.je; o1 = s.cmin;
             return BS_SUBS_FULL;
         }
-        if (indel1) { o0 = s.je; o1 = s.cmin * 2 + (s.edel ? 1 : 0); return BS_INDEL1_FULL; }
+        if (indel1) { o0 = s.je; o1 = s.cmin * 2 + (edel ? 1 : 0); return BS_INDEL1_FULL; }
         const int s0 = s.jfa - reach;
         o0 = s0 > dp_lo ? s0 : dp_lo;
         o1 = s.jla * 2;
@@ -502,11 +518,11 @@ CAH_HD int bs_finish_rows(const BackScanBook& s, const BsLastColumn<W, X>& col, 
         return BS_DP;
     }
     // substitutions only (see the header): the diagonal (0, je - m) .. (m, je) lies inside the window
-    if (s.cmin >= 1 && s.eclean && s.je - p.m >= j0 && s.je - s.jfa <= p.half_m - p.kacc && !tail_may_win) {
+    if (s.cmin >= 1 && eclean && s.je - p.m >= j0 && s.je - s.jfa <= p.half_m - p.kacc && !tail_may_win) {
         o0 = s.je; o1 = s.cmin;
         return BS_SUBS_FULL;
     }
-    if (indel1 && !tail_may_win1) { o0 = s.je; o1 = s.cmin * 2 + (s.edel ? 1 : 0); return BS_INDEL1_FULL; }
+    if (indel1 && !tail_may_win1) { o0 = s.je; o1 = s.cmin * 2 + (edel ? 1 : 0); return BS_INDEL1_FULL; }
     const int s0 = s.jfa - reach;
     o0 = s0 > dp_lo ? s0 : dp_lo;
     o1 = best_i == 0 ? s.jla * 2 : n * 2 + 1;

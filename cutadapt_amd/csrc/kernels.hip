@@ -1892,12 +1892,16 @@ __global__ __launch_bounds__(256, (KIND == 3 || KIND == 0) ? 4 : CAH_SCAN_WAVES)
             typename std::conditional<KIND == 0, BackScanState, BackScanState32<XR>>::type st;
             if constexpr (KIND == 0) bs_init(st, p); else bs32_init(st, p);
             // one column: the character's table entry is the 64-bit match word, or {rows 1..32, rows 33..}
-            auto step = [&](const uint64_t eq, const int jj, const int joff = 0) -> bool {
-                if constexpr (KIND == 0) return bs_step<!MULTI>(st, eq, jj + joff, p);
-                else return bs32_step<!MULTI, XR>(st, (uint32_t)eq, (uint32_t)(eq >> 32), jj, p, 0x7FFFFFFF, joff);
+            // (the column loop carries NO predicate from column to column: the first column that finishes the read as
+            // EXACT_FULL is noted in exact_j inside the step's rare booking branch, `done` changes once per chunk.  As
+            // bools they were lane masks in scalar register pairs, merged with scalar instructions behind every column's
+            // branch -- three per column in the unguarded body, forty in the guarded one; profiles/r07.)
+            int j = j0, exact_j = -1;
+            auto step = [&](const uint64_t eq, const int jj, const int joff) {
+                if constexpr (KIND == 0) bs_step<!MULTI>(st, eq, jj + joff, p, &exact_j);
+                else bs32_step<!MULTI, XR>(st, (uint32_t)eq, (uint32_t)(eq >> 32), jj, p, 0x7FFFFFFF, joff, &exact_j);
             };
-            int j = j0, exact_j = 0;
-            bool done = !valid, exact = false, stopped = false, retry = false, valid_out = valid;
+            bool done = !valid, stopped = false, retry = false, valid_out = valid;
             int retry_at = MULTI ? 0 : a.retry_threshold;
             // one 16-character chunk per iteration (per lane: its own window start), the next chunk requested
             // before this one is consumed, the LDS lookup of the next column's match word issued one column
@@ -1974,21 +1978,23 @@ __global__ __launch_bounds__(256, (KIND == 3 || KIND == 0) ? 4 : CAH_SCAN_WAVES)
                     for (int t = 0; t < 16; ++t) {
                         const uint64_t eq = eqq[t % SCAN_AHEAD];
                         if (t + SCAN_AHEAD < 16) eqq[t % SCAN_AHEAD] = eq_of(cur, t + SCAN_AHEAD);
-                        if (step(eq, j, t + 1) && !exact) { exact = true; exact_j = j + t + 1; }
+                        step(eq, j, t + 1);
                     }
                     j += 16;
-                    if (exact) done = true;
                 } else {
+                    // a lane takes the first `rem` columns of the chunk: one compare with a constant per column.  (A lane
+                    // that finishes as EXACT_FULL inside the chunk steps on to its read's end; its state is not looked at
+                    // again and exact_j keeps the first such column.)
+                    const int rem = done ? 0 : n - j;
 #pragma unroll
                     for (int t = 0; t < 16; ++t) {
                         const uint64_t eq = eqq[t % SCAN_AHEAD];
                         if (t + SCAN_AHEAD < 16) eqq[t % SCAN_AHEAD] = eq_of(cur, t + SCAN_AHEAD);
-                        if (!done && j < n) {
-                            ++j;
-                            if (step(eq, j)) { exact = true; exact_j = j; done = true; }
-                        }
+                        if (t < rem) step(eq, j, t + 1);
                     }
+                    j += min(max(rem, 0), 16);
                 }
+                if (exact_j >= 0) done = true;
                 pos += 16;
                 cur = nxt;
                 if constexpr (!MULTI) {
@@ -2011,6 +2017,7 @@ __global__ __launch_bounds__(256, (KIND == 3 || KIND == 0) ? 4 : CAH_SCAN_WAVES)
 
             int o0 = 0, o1 = 0;
             int cls = BS_NONE;
+            const bool exact = exact_j >= 0;
             // the classification -- above all the walk down the last column's rows -- only for lanes whose result it is:
             // a lane that ended as EXACT_FULL, was set aside or never had a read skips it, and a wave made of such lanes
             // (the common wave of reads with the adapter inside) skips the row loop altogether
